@@ -7,7 +7,13 @@ batch (evm_apply_batch: pack + canonical check + murmur3, cross-cell PK
 check, LWW walks, Merkle fold) with the inputs already resident in HBM,
 starting from an empty tree.
 
-At N = 1 the same line carries the other BASELINE configs under extra keys:
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+batches (HIP events around the dominant kernel's launches, chosen from a
+profiled pass of at most 20 batches: its roofline) and prints the headline line;
+`--dump-outputs DIR` also writes what the last timed batch returned.  `--full`
+adds what takes runs of its own: the per-kernel breakdown over N batches, the
+host-to-host steps, the CPU baseline, and at N = 1 the other BASELINE configs
+under extra keys of the same line:
   "client_adversarial": config 5 on the client side (equal-millis ties,
              exact and stale redeliveries, upper-case nodes), 10M messages,
              pipelined like the headline, its own roofline;
@@ -108,6 +114,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--messages", type=int, default=10_000_000)
     ap.add_argument("--cells", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="the headline run with everything around it: the per-kernel breakdown over --steps batches, "
+                         "the host-to-host steps, the CPU baselines and (at N=1) the config 1, 3, 4 and 5 legs; "
+                         "without it the headline run only warms up, times --steps batches and prints its line with "
+                         "the timed region's roofline (--extra, --cpu-seconds, --e2e and --reingest then have no "
+                         "effect)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline run: after the timed steps write what the last timed batch returned (flags, "
+                         "winners, the Merkle tree's leaves and root) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget per leg (0: skip)")
     ap.add_argument("--overlap", type=int, default=1, help="EVM_OPT_OVERLAP: independent checks on a second stream")
     ap.add_argument("--depth", type=int, default=4, help="config 2: batches in flight (evm_apply_batch_async)")
@@ -397,6 +412,41 @@ def progress(what):
 
 T_START = time.perf_counter()
 
+DUMP_MAX_FLAGS = 10_000_000  # float32: 40 MB (the default batch whole)
+DUMP_MAX_OTHER = 500_000  # float64: 4 MB each of winners, leaf codes (two halves) and leaf XORs; < 64 MB in all
+
+
+def dump_outputs(path, flags, winner, tree):
+    """--dump-outputs: what the last timed batch returned to its caller, as
+    path/<name>.npy -- the per-message flags (float32), the per-cell winner
+    indexes, and the batch's Merkle tree as its leaf list (minute codes as
+    two 32-bit halves, leaf XORs) and root (float64: every value exact).  An
+    array above its DUMP_MAX_* is written as a seeded sample of its elements,
+    the same positions in every run."""
+    import numpy as np
+
+    def sample(x, cap=DUMP_MAX_OTHER):
+        if x.shape[0] <= cap:
+            return x
+        at = np.sort(np.random.default_rng(0xE7D0).choice(x.shape[0], cap, replace=False))
+        return x[at]
+
+    os.makedirs(path, exist_ok=True)
+    off, code, xr = tree.leaves()
+    root, present = tree.roots()
+    code = sample(code)
+    arrays = {
+        "flags": sample(flags.cpu().numpy(), DUMP_MAX_FLAGS).astype(np.float32),
+        "winner": sample(winner.cpu().numpy()).astype(np.float64),
+        "tree_leaf_offsets": off.astype(np.float64),
+        "tree_leaf_code_hi": (code >> np.uint64(32)).astype(np.float64),
+        "tree_leaf_code_lo": (code & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "tree_leaf_xor": sample(xr).astype(np.float64),
+        "tree_root": np.where(present, root, 0).astype(np.float64),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
 
 def main():
     global TRAFFIC_DIR
@@ -523,9 +573,11 @@ def main():
     host_us = {"enqueue": [], "wait": []}
 
     def run_pipelined(k_steps):
+        """-> what the last batch's wait returned (flags, winner, tree, status); its tree is the caller's to free."""
         import collections
 
         q = collections.deque()
+        last = None
         for k in range(k_steps):
             if len(q) == DEPTH:
                 w0 = time.perf_counter()
@@ -535,21 +587,28 @@ def main():
             q.append(eng.apply_batch_async(empty, ts, cell, a.cells, *outs[k % DEPTH]))
             host_us["enqueue"].append((time.perf_counter() - e0) * 1e6)
         while q:
-            q.popleft().wait()[2].free()
+            last = q.popleft().wait()
+            if q:
+                last[2].free()
+        return last
 
     eng.prof_enable(True)  # warmup with events on: fills the engine's event pool
     for _ in range(a.warmup):
         step().free()
-    run_pipelined(max(a.warmup, 2))
+    run_pipelined(max(a.warmup, 2))[2].free()
     torch.cuda.synchronize()
     # per-kernel breakdown (untimed, an event pair around every launch): picks
-    # the dominant main-stream kernel
+    # the dominant main-stream kernel -- over as many batches as are timed with
+    # --full (the breakdown is reported); a plain run needs only the choice (the
+    # timed region carries that kernel's events) but keeps up to 20 of these
+    # batches, ~0.4 ms each: the timed window has always started right after them
+    n_prof = a.steps if a.full else min(a.steps, 20)
     eng.prof_reset()
     u0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(n_prof):
         step().free()
     torch.cuda.synchronize()
-    ms_all_events = (time.perf_counter() - u0) / a.steps * 1e3
+    ms_all_events = (time.perf_counter() - u0) / n_prof * 1e3
     prof = eng.prof_report()
     dom = dominant(prof, ALG_BYTES_PER_MSG, SIDE_KERNELS if a.overlap else ())
     # timed region: events only around the dominant kernel's launches
@@ -563,17 +622,21 @@ def main():
     host_us["wait"].clear()
     st0 = eng.stats()
     t0 = time.perf_counter()
-    run_pipelined(a.steps)
+    last = run_pipelined(a.steps)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     st1 = eng.stats()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *last[:3])
+    last[2].free()
+    del last
     # the path the timed batches took: every one on the tc streaming path, none redone
     path = {k: st1[k] - st0[k] for k in ("tc_batches", "tc_redos", "small_batches", "small_fallbacks")}
     path["batches"] = a.steps
     path["kernels"] = sorted(prof)
-    if not a.dom_events:  # the dominant kernel's duration from an identical pass
+    if a.full and not a.dom_events:  # the dominant kernel's duration from an identical pass
         eng.prof_enable(True)
-        run_pipelined(a.steps)
+        run_pipelined(a.steps)[2].free()
         torch.cuda.synchronize()
     eng.prof_enable(False)
     eng.prof_only(None)
@@ -584,37 +647,29 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
     prof_dom = eng.prof_report()
-    # host-to-host (never `value`): the batch in pinned host memory, H2D of
-    # timestamps + cells, the step, D2H of flags + winners -- what a caller
-    # that hands over host buffers (the N-API addon) sees
-    ts_h = torch.from_numpy(ts_np).pin_memory()
-    cell_h = torch.from_numpy(np.ascontiguousarray(cell_np).view(np.int32)).pin_memory()
-    flags_h = torch.empty(a.messages, dtype=torch.uint8).pin_memory()
-    win_h = torch.empty(a.cells, dtype=torch.int32).pin_memory()
-    reps = max(1, min(a.steps, 5))
-    torch.cuda.synchronize()
-    h0 = time.perf_counter()
-    for _ in range(reps):
-        ts.copy_(ts_h, non_blocking=True)
-        cell.view(torch.int32).copy_(cell_h, non_blocking=True)
-        step().free()
-        flags_h.copy_(flags, non_blocking=True)
-        win_h.copy_(winner, non_blocking=True)
-    torch.cuda.synchronize()
-    ms_h2h = (time.perf_counter() - h0) / reps * 1e3
+    if a.full:
+        # host-to-host (never `value`): the batch in pinned host memory, H2D of
+        # timestamps + cells, the step, D2H of flags + winners -- what a caller
+        # that hands over host buffers (the N-API addon) sees
+        ts_h = torch.from_numpy(ts_np).pin_memory()
+        cell_h = torch.from_numpy(np.ascontiguousarray(cell_np).view(np.int32)).pin_memory()
+        flags_h = torch.empty(a.messages, dtype=torch.uint8).pin_memory()
+        win_h = torch.empty(a.cells, dtype=torch.int32).pin_memory()
+        reps = max(1, min(a.steps, 5))
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        for _ in range(reps):
+            ts.copy_(ts_h, non_blocking=True)
+            cell.view(torch.int32).copy_(cell_h, non_blocking=True)
+            step().free()
+            flags_h.copy_(flags, non_blocking=True)
+            win_h.copy_(winner, non_blocking=True)
+        torch.cuda.synchronize()
+        ms_h2h = (time.perf_counter() - h0) / reps * 1e3
 
     if rank == 0:
         ms_step = elapsed / a.steps * 1e3
         value = world * a.messages * a.steps / elapsed
-        # dominant kernel and its roofline, from the timed region's events
-        tot_ms, launches = prof_dom[dom]
-        avg_s = tot_ms / launches / 1e3
-        alg = ALG_BYTES_PER_MSG[dom] * a.messages
-        achieved = alg / avg_s
-        roof = {"bound": "hbm", "kernel": dom, "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK, "traffic": traffic_of(dom, "client"),
-                "kernel_ms_avg": avg_s * 1e3, "alg_bytes_per_launch": alg,
-                "kernel_share_of_step": tot_ms / (ms_step * a.steps)}
         out = {
             "metric": METRIC,
             "value": value,
@@ -631,17 +686,29 @@ def main():
             "config": {"workload": "config2: applyMessages, 1 owner per GPU, %d msgs, %d cells, 64 nodes, shuffled"
                        % (a.messages, a.cells), "messages_per_gpu": a.messages, "cells": a.cells,
                        "parallelism": "owner-sharded, %d rank(s)" % world},
-            "roofline": roof,
             "path": path,
-            "pipeline": {"alg_bytes_per_msg": 120, "ms_per_step_all_kernel_events": ms_all_events,
-                         "batches_in_flight": DEPTH,
+            "pipeline": {"alg_bytes_per_msg": 120, "batches_in_flight": DEPTH,
                          "host_enqueue_us_avg": sum(host_us["enqueue"]) / max(1, len(host_us["enqueue"])),
                          "host_wait_us_avg": sum(host_us["wait"]) / max(1, len(host_us["wait"])),
-                         "host_to_host_ms_per_step": ms_h2h, "host_to_host_msgs_per_s": a.messages / ms_h2h * 1e3,
-                         "pipeline_hbm_frac": 120 * a.messages / (elapsed / a.steps) / HBM_PEAK,
-                         "kernels_ms_per_step": {k: v[0] / a.steps for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}},
+                         "pipeline_hbm_frac": 120 * a.messages / (elapsed / a.steps) / HBM_PEAK},
             "cpu_baseline": None,
+            "full": a.full,
         }
+    if rank == 0 and dom in prof_dom:
+        # dominant kernel and its roofline, from the timed region's events
+        tot_ms, launches = prof_dom[dom]
+        avg_s = tot_ms / launches / 1e3
+        alg = ALG_BYTES_PER_MSG[dom] * a.messages
+        achieved = alg / avg_s
+        out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": traffic_of(dom, "client"),
+                           "kernel_ms_avg": avg_s * 1e3, "alg_bytes_per_launch": alg,
+                           "kernel_share_of_step": tot_ms / (ms_step * a.steps)}
+    if rank == 0 and a.full:
+        out["pipeline"].update({
+            "ms_per_step_all_kernel_events": ms_all_events,
+            "host_to_host_ms_per_step": ms_h2h, "host_to_host_msgs_per_s": a.messages / ms_h2h * 1e3,
+            "kernels_ms_per_step": {k: v[0] / a.steps for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}})
         if world == 1 and a.cpu_seconds > 0:
             progress("cpu baseline")
             out["cpu_baseline"] = cpu_baseline(ts_np, cell_np, a.cpu_seconds)
@@ -670,6 +737,7 @@ def main():
             out["config5_shape"] = config5_shape_leg(eng5, a)
             eng5.close()
             torch.cuda.empty_cache()
+    if rank == 0:
         emit(out)
     if world > 1:
         dist.destroy_process_group()

@@ -8,11 +8,11 @@ mkdir -p "$O"
 export PYTHONUNBUFFERED=1
 set -e
 echo "bench"
-timeout -k 10 600 python3 -u "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 600 python3 -u "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err"
 tail -c 600 "$O/bench.json"
 echo "rocprof stats"
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- \
-  python3 "$R/bench.py" > "$O/prof_bench.json" 2> "$O/prof_bench.err")
+  python3 "$R/bench.py" --full > "$O/prof_bench.json" 2> "$O/prof_bench.err")
 find "$O/prof" -name "*kernel_stats.csv" -exec cp {} "$O/kernel_stats.csv" \;
 find "$O/prof" -name "*kernel_trace.csv" -delete
 echo "pytest"
