@@ -24,6 +24,7 @@ EVM_EDIST = 9
 EVM_ESTATE = 10
 EVM_EROUNDS = 11
 EVM_EHANDOVER = 12
+EVM_ESNAPSHOT = 13
 SYNC_HOST = 0
 SYNC_DEVICE = 1
 DIST_ID_BYTES = 128
@@ -134,6 +135,11 @@ SIGNATURES = {
     "evm_sync_log_read": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "evm_sync_next_id": (C.c_uint64, [_vp]),
     "evm_sync_timing": (_i, [_vp, _vp]),
+    "evm_sync_log_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "evm_sync_compact": (_i, [_vp, _vp, C.c_uint64, _vp]),
+    "evm_sync_save": (_i, [_vp, C.c_char_p, _vp, C.c_uint64]),
+    "evm_sync_load": (_i, [_vp, _vp, C.c_char_p, C.POINTER(_vp), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "evm_snapshot_info": (_i, [C.c_char_p, _vp]),
     "evm_store_since": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "evm_server_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "evm_store_select_after": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -175,6 +181,14 @@ SIGNATURES = {
         [_vp, _vp, _vp, _sz, _sz, _vp, _u32, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, C.POINTER(_vp)],
     ),
 }
+
+
+class SnapshotInfo(C.Structure):
+    """struct evm_snapshot_info"""
+
+    _fields_ = [("version", C.c_uint32), ("users", C.c_uint64), ("rows", C.c_uint64),
+                ("content_bytes", C.c_uint64), ("blob_bytes", C.c_uint64)]
+
 
 _LIB = None
 

@@ -1042,6 +1042,7 @@ const char* evm_strerror(int s) {
     case EVM_ESTATE: return "a store invariant broke in a merge; nothing committed";
     case EVM_EROUNDS: return "a userId in two requests of one call: split the call into rounds";
     case EVM_EHANDOVER: return "request not modelled here: the caller's reference path runs it";
+    case EVM_ESNAPSHOT: return "snapshot file damaged, truncated, of an unknown version, or its roots do not match";
   }
   return "unknown status";
 }
@@ -1384,6 +1385,18 @@ int evm_tree_roots(evm_ctx* ctx, const evm_tree* t, int32_t* root, uint8_t* pres
   HIPR(hipMemcpyAsync(present, dp, t->n_owners, hipMemcpyDeviceToHost, ctx->stream));
   return hip_ok(hipStreamSynchronize(ctx->stream));
 }
+
+}  // extern "C"
+
+// evm_tree_roots with the results left on the device (n = the tree's owners)
+int evm::tree_roots_dev(evm_ctx* ctx, const evm_tree* t, int32_t* root_dev, uint8_t* present_dev) {
+  if (t->n_owners == 0) return EVM_OK;
+  KLAUNCH(k_roots, dim3(grid_for(t->n_owners, 256)), dim3(256), t->off, t->end, t->pfx, t->n_owners, root_dev,
+          present_dev);
+  return EVM_OK;
+}
+
+extern "C" {
 
 int evm_merkle_insert(evm_ctx* ctx, const evm_tree* in, const char* ts, size_t stride, size_t n, const uint32_t* owner,
                       evm_tree** out) {

@@ -477,4 +477,17 @@ __device__ __forceinline__ void wire_load(const WireSrc& w, size_t i, u64* tc, u
 int server_ingest_wire(evm_ctx* ctx, evm_store* s, const WireSrc& w, size_t n, const u32* owner, uint64_t id_base,
                        uint8_t* flags);
 
+// The store's rows as the message log's compaction and snapshot read them
+// (device arrays in (owner, timestamp) order; id is rewritten in place by the
+// compaction's last step).
+struct StoreRows {
+  u32 n_owners;
+  u64 n;
+  const u32* owner;  // [n]
+  u64* id;           // [n]
+};
+void store_rows(evm_store* s, StoreRows* out);        // evm_server.hip
+int store_reset(evm_ctx* ctx, evm_store* s);          // the store emptied (as evm_store_new left it)
+int tree_roots_dev(evm_ctx* ctx, const evm_tree* t, int32_t* root_dev, uint8_t* present_dev);  // evm_engine.hip
+
 }  // namespace evm

@@ -3079,6 +3079,37 @@ int evm_store_messages(evm_ctx* ctx, const evm_store* s, uint64_t* owner_off, ui
 
 }  // extern "C"
 
+void evm::store_rows(evm_store* s, StoreRows* out) {
+  out->n_owners = s->n_owners;
+  out->n = s->n;
+  out->owner = s->owner;
+  out->id = s->id;
+}
+
+int evm::store_reset(evm_ctx* ctx, evm_store* s) {
+  evm_store ns{};
+  evm_tree* nt = nullptr;
+  int st = store_alloc(ctx, &ns, s->n_owners, 0);
+  if (!st) st = hip_ok(hipMemsetAsync(ns.off, 0, sizeof(u64) * (s->n_owners + 1), ctx->stream));
+  if (!st) st = evm_tree_new(ctx, s->n_owners, &nt);
+  if (st) {
+    store_release_arrays(ctx, &ns);
+    return st;
+  }
+  store_release_arrays(ctx, s);
+  if (s->tree) tree_destroy(ctx, s->tree);
+  s->n = 0;
+  s->bytes = ns.bytes;
+  s->off = ns.off;
+  s->owner = ns.owner;
+  s->tc = ns.tc;
+  s->hi = ns.hi;
+  s->lo = ns.lo;
+  s->id = ns.id;
+  s->tree = nt;
+  return evm_sync(ctx);
+}
+
 // Swap in the new store arrays and tree.
 static int commit_store(evm_ctx* ctx, evm_store* s, evm_store& ns, evm_tree* new_tree) {
   store_release_arrays(ctx, s);

@@ -20,8 +20,10 @@
 // way (evm_sync_fetch).  Nothing in the round is a torch call.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <chrono>
@@ -32,6 +34,7 @@
 #include "evm_device.hpp"
 #include "evm_internal.hpp"
 #include "evm_prims.hpp"
+#include "evm_snapshot.hpp"
 
 using namespace evm;
 
@@ -332,6 +335,153 @@ __global__ void k_log_content(const LSeg* __restrict__ sg, u32 ns, const u64* __
   }
 }
 
+// ---- log compaction (evm_sync_compact).  live[id] counts the store's rows
+// that hold old id `id` (1 for a live row; an id outside the log or counted
+// twice is a broken invariant); its exclusive scan in place is the id map:
+// map[id] = the live ids below id, map[M] = the live rows, and id is live
+// where map[id + 1] != map[id].
+__global__ void k_cmp_mark(const u64* __restrict__ ids, u64 n, u64 M, u64* __restrict__ live, u32* __restrict__ bad) {
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+    const u64 id = ids[i];
+    if (id >= M) atomicOr(bad, 1u);
+    else if (atomicAdd(&live[id], 1ull)) atomicOr(bad, 2u);
+  }
+}
+// each new row's old id, and the live rows' content bytes summed
+__global__ void k_cmp_rows(const LSeg* __restrict__ sg, u32 ns, const u64* __restrict__ map, u64 M, u64 n,
+                           u64* __restrict__ oldid, u64* __restrict__ total) {
+  u64 sum = 0;
+  for (u64 id = blockIdx.x * (u64)blockDim.x + threadIdx.x; id < M; id += (u64)gridDim.x * blockDim.x) {
+    const u64 r = map[id];
+    if (map[id + 1] == r || r >= n) continue;
+    const int s = lseg_of(sg, ns, id);
+    if (s < 0 || id - sg[s].base >= sg[s].n) continue;  // (the segments cover [0, M): never)
+    const u64 k = id - sg[s].base;
+    oldid[r] = id;
+    sum += sg[s].coff[k + 1] - sg[s].coff[k];
+  }
+  for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
+}
+__global__ void k_cmp_len(const LSeg* __restrict__ sg, u32 ns, const u64* __restrict__ oldid, u64 n,
+                          u64* __restrict__ clen) {
+  for (u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x; r < n; r += (u64)gridDim.x * blockDim.x) {
+    const u64 id = oldid[r];
+    const int s = lseg_of(sg, ns, id);
+    const u64 k = id - sg[s].base;
+    clen[r] = sg[s].coff[k + 1] - sg[s].coff[k];
+  }
+}
+// the 48-B timestamp rows: one 16-B piece per thread (rows are 16-B aligned in
+// every segment; neighbouring threads read and write neighbouring pieces)
+__global__ void k_cmp_ts(const LSeg* __restrict__ sg, u32 ns, const u64* __restrict__ oldid, u64 n,
+                         uint4* __restrict__ out) {
+  for (u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x; t < 3 * n; t += (u64)gridDim.x * blockDim.x) {
+    const u64 r = t / 3;
+    const u32 j = (u32)(t - 3 * r);
+    const u64 id = oldid[r];
+    const int s = lseg_of(sg, ns, id);
+    out[t] = reinterpret_cast<const uint4*>(sg[s].ts + (id - sg[s].base) * 48)[j];
+  }
+}
+// the contents: one 16-B piece of the NEW arena per thread, stored whole.  A
+// piece inside one row is two aligned 16-B loads of the old arena shifted
+// into place (the arenas are readable in whole 16-B chunks, 16 B of slack);
+// a piece that spans rows (short contents) is read byte by byte.
+struct CmpSrc {
+  const uint8_t* p;  // the row's first content byte in its old segment
+};
+__device__ __forceinline__ CmpSrc cmp_src(const LSeg* sg, u32 ns, const u64* oldid, u64 r) {
+  const u64 id = oldid[r];
+  const int s = lseg_of(sg, ns, id);
+  return CmpSrc{sg[s].content + sg[s].coff[id - sg[s].base]};
+}
+__global__ void k_cmp_content(const LSeg* __restrict__ sg, u32 ns, const u64* __restrict__ oldid,
+                              const u64* __restrict__ ncoff, u64 n, u64 CB, uint4* __restrict__ out) {
+  const u64 nchunk = (CB + 15) / 16;
+  for (u64 c = blockIdx.x * (u64)blockDim.x + threadIdx.x; c < nchunk; c += (u64)gridDim.x * blockDim.x) {
+    const u64 b0 = c * 16;
+    u64 lo = 0, hi = n;  // the first row boundary above b0 (ncoff[n] = CB > b0)
+    while (lo < hi) {
+      const u64 mid = (lo + hi) >> 1;
+      if (ncoff[mid] <= b0) lo = mid + 1;
+      else hi = mid;
+    }
+    u64 r = lo - 1;  // ncoff[r] <= b0 < ncoff[r + 1]
+    CmpSrc src = cmp_src(sg, ns, oldid, r);
+    u64 start = ncoff[r], end = ncoff[r + 1];
+    uint4 v;
+    if (b0 + 16 <= end) {
+      const uint8_t* p = src.p + (b0 - start);
+      const u32 sh = (u32)(reinterpret_cast<uintptr_t>(p) & 15);
+      const uint4* q = reinterpret_cast<const uint4*>(p - sh);
+      const uint4 a = q[0];
+      const uint4 b = sh ? q[1] : a;
+      const u64 w0 = (u64)a.x | ((u64)a.y << 32), w1 = (u64)a.z | ((u64)a.w << 32);
+      const u64 w2 = (u64)b.x | ((u64)b.y << 32), w3 = (u64)b.z | ((u64)b.w << 32);
+      const bool up = sh >= 8;
+      const u32 bits = (sh & 7) * 8;
+      const u64 s0 = up ? w1 : w0, s1 = up ? w2 : w1, s2 = up ? w3 : w2;
+      const u64 o0 = bits ? (s0 >> bits) | (s1 << (64 - bits)) : s0;
+      const u64 o1 = bits ? (s1 >> bits) | (s2 << (64 - bits)) : s1;
+      v = make_uint4((u32)o0, (u32)(o0 >> 32), (u32)o1, (u32)(o1 >> 32));
+    } else {
+      u32 x[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (u32 i = 0; i < 16; ++i) {
+        const u64 b = b0 + i;
+        if (b < CB) {
+          while (b >= end) {  // (b < CB = ncoff[n]: r stays below n)
+            ++r;
+            start = end;
+            end = ncoff[r + 1];
+            if (b < end) src = cmp_src(sg, ns, oldid, r);
+          }
+          x[i >> 2] |= (u32)src.p[b - start] << (8 * (i & 3));
+        }
+      }
+      v = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+    out[c] = v;
+  }
+}
+// the commit: the store's ids through the map; the ids a caller asked about
+__global__ void k_cmp_remap(u64* __restrict__ ids, u64 n, const u64* __restrict__ map) {
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) ids[i] = map[ids[i]];
+}
+__global__ void k_cmp_moved(const u64* __restrict__ ask, u64 na, const u64* __restrict__ map, u64 M,
+                            u64* __restrict__ moved) {
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < na; i += (u64)gridDim.x * blockDim.x) {
+    const u64 id = ask[i];
+    moved[i] = (id < M && map[id + 1] != map[id]) ? map[id] : ~0ull;
+  }
+}
+
+// ---- snapshot (evm_sync_save / evm_sync_load)
+// each log row's owner slot: the store's (owner, id) columns inverted
+__global__ void k_snap_owner(const u32* __restrict__ owner, const u64* __restrict__ id, u64 n, u32* __restrict__ out,
+                             u32* __restrict__ bad) {
+  for (u64 p = blockIdx.x * (u64)blockDim.x + threadIdx.x; p < n; p += (u64)gridDim.x * blockDim.x) {
+    const u64 i = id[p];
+    if (i < n) out[i] = owner[p];
+    else atomicOr(bad, 1u);
+  }
+}
+__global__ void k_snap_all_ins(const uint8_t* __restrict__ flags, u64 n, u32* __restrict__ bad) {
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
+    if (!(flags[i] & EVM_MSG_INS)) atomicOr(bad, 1u);
+}
+// the rebuilt roots against the saved ones (owners past the saved users: no tree)
+__global__ void k_snap_roots(const int32_t* __restrict__ root, const uint8_t* __restrict__ present, u32 O,
+                             const int32_t* __restrict__ want_root, const uint8_t* __restrict__ want_present, u32 users,
+                             u32* __restrict__ bad) {
+  for (u32 o = blockIdx.x * blockDim.x + threadIdx.x; o < O; o += gridDim.x * blockDim.x) {
+    const int32_t wr = o < users ? want_root[o] : 0;
+    const uint8_t wp = o < users ? want_present[o] : 0;
+    if (root[o] != wr || (present[o] != 0) != (wp != 0)) atomicOr(bad, 1u);
+  }
+}
+
 template <typename F>
 void host_parallel(size_t n, int threads, F f) {  // f(begin, end) over disjoint runs of [0, n)
   const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)threads, n / ((size_t)1 << 20) + 1));
@@ -419,6 +569,62 @@ int stage_d2h(evm_ctx* ctx, void* dst, const void* src, size_t bytes) {
   return EVM_OK;
 }
 
+// device -> a host sink, chunk by chunk through the pinned ring (the copy
+// engine fills chunk k + 1 while sink(p, m) consumes chunk k)
+template <typename F>
+int stage_d2h_each(evm_ctx* ctx, const void* src, size_t bytes, F sink) {
+  HostStage* h;
+  int st = stage_get(ctx, &h);
+  if (st) return st;
+  HIPR(hipEventRecord(h->ev[0], ctx->stream));  // (src is written on ctx->stream)
+  HIPR(hipStreamWaitEvent(h->cs, h->ev[0], 0));
+  const size_t nk = (bytes + HostStage::CHUNK - 1) / HostStage::CHUNK;
+  auto issue = [&](size_t k) -> int {
+    const int b = (int)(k % HostStage::NB);
+    const size_t a = k * HostStage::CHUNK, m = std::min(HostStage::CHUNK, bytes - a);
+    HIPR(hipMemcpyAsync(h->pin[b], static_cast<const uint8_t*>(src) + a, m, hipMemcpyDeviceToHost, h->cs));
+    HIPR(hipEventRecord(h->ev[b], h->cs));
+    return EVM_OK;
+  };
+  for (size_t k = 0; !st && k < nk && k < (size_t)HostStage::NB - 1; ++k) st = issue(k);
+  for (size_t k = 0; !st && k < nk; ++k) {
+    const int b = (int)(k % HostStage::NB);
+    st = hip_ok(hipEventSynchronize(h->ev[b]));
+    const size_t a = k * HostStage::CHUNK, m = std::min(HostStage::CHUNK, bytes - a);
+    if (!st) st = sink(static_cast<const uint8_t*>(h->pin[b]), m);
+    if (!st && k + HostStage::NB - 1 < nk) st = issue(k + HostStage::NB - 1);
+  }
+  if (st) (void)hipStreamSynchronize(h->cs);  // (no copy still lands in a chunk after a failure)
+  return st;
+}
+
+// a host source -> device the same way: fill(p, m) writes chunk k + 1 while
+// the copy engine moves chunk k; ctx->stream waits for the last chunk
+template <typename F>
+int stage_h2d_each(evm_ctx* ctx, void* dst, size_t bytes, F fill) {
+  HostStage* h;
+  int st = stage_get(ctx, &h);
+  if (st) return st;
+  HIPR(hipEventRecord(h->ev[0], ctx->stream));  // (dst may have been allocated or written on ctx->stream)
+  HIPR(hipStreamWaitEvent(h->cs, h->ev[0], 0));
+  size_t k = 0;
+  for (size_t a = 0; !st && a < bytes; a += HostStage::CHUNK, ++k) {
+    const int b = (int)(k % HostStage::NB);
+    const size_t m = std::min(HostStage::CHUNK, bytes - a);
+    st = hip_ok(hipEventSynchronize(h->ev[b]));  // (the chunk's previous transfer is done with it)
+    if (!st) st = fill(h->pin[b], m);
+    if (!st) st = hip_ok(hipMemcpyAsync(static_cast<uint8_t*>(dst) + a, h->pin[b], m, hipMemcpyHostToDevice, h->cs));
+    if (!st) st = hip_ok(hipEventRecord(h->ev[b], h->cs));
+  }
+  if (st) {
+    (void)hipStreamSynchronize(h->cs);  // (dst may be freed by the caller)
+    return st;
+  }
+  HIPR(hipEventRecord(h->ev[0], h->cs));
+  HIPR(hipStreamWaitEvent(ctx->stream, h->ev[0], 0));
+  return EVM_OK;
+}
+
 }  // namespace
 
 void evm_host_stage_free(evm_ctx* ctx) {
@@ -442,6 +648,7 @@ struct SyncSeg {
   uint8_t* content;
   void* block;
   size_t bytes;
+  u64 cb;  // content bytes
 };
 
 struct evm_sync_server {
@@ -518,6 +725,7 @@ int seg_alloc(evm_sync_server* s, u64 n, u64 cb, SyncSeg* g) {
   if (!p) return EVM_ENOMEM;
   g->base = s->next_id;
   g->n = n;
+  g->cb = cb;
   g->ts = static_cast<uint8_t*>(p);
   g->coff = reinterpret_cast<u64*>(static_cast<uint8_t*>(p) + a);
   g->content = static_cast<uint8_t*>(p) + a + b;
@@ -1144,5 +1352,347 @@ int evm_sync_log_read(evm_sync_server* s, const uint64_t* ids, uint64_t n, char*
 }
 
 uint64_t evm_sync_next_id(const evm_sync_server* s) { return s ? s->next_id : 0; }
+
+int evm_sync_log_info(const evm_sync_server* s, uint32_t* n_segments, uint64_t* n_rows, uint64_t* content_bytes) {
+  if (!s) return EVM_EINVAL;
+  if (n_segments) *n_segments = (uint32_t)s->segs.size();
+  if (n_rows) *n_rows = s->next_id;
+  if (content_bytes) {
+    u64 cb = 0;
+    for (const auto& g : s->segs) cb += g.cb;
+    *content_bytes = cb;
+  }
+  return EVM_OK;
+}
+
+int evm_sync_compact(evm_sync_server* s, const uint64_t* ask, uint64_t n_ask, uint64_t* moved_to) {
+  if (!s || (n_ask && (!ask || !moved_to))) return EVM_EINVAL;
+  evm_ctx* ctx = s->ctx;
+  StoreRows rows;
+  store_rows(s->store, &rows);
+  const u64 M = s->next_id, n = rows.n;
+  if (n > M) return EVM_ESTATE;
+  if (s->segs.size() <= 1 && n == M) {  // (compact already: every id is live and keeps its place)
+    for (u64 i = 0; i < n_ask; ++i) moved_to[i] = ask[i] < M ? ask[i] : UINT64_MAX;
+    return EVM_OK;
+  }
+  Scratch S(ctx);
+  const u32 ns = (u32)s->segs.size();
+  std::vector<LSeg> hs(ns);
+  for (u32 k = 0; k < ns; ++k)
+    hs[k] = LSeg{s->segs[k].base, s->segs[k].n, s->segs[k].ts, s->segs[k].coff, s->segs[k].content};
+  // ---- everything the compaction needs, before anything changes
+  LSeg* sg = S.alloc<LSeg>(ns);
+  u64* map = S.alloc<u64>(M + 1);
+  u64* oldid = S.alloc<u64>(n);
+  u64* total = S.alloc<u64>(1);
+  u32* bad = S.alloc<u32>(1);
+  u64* ask_d = S.alloc<u64>(n_ask);
+  u64* moved_d = S.alloc<u64>(n_ask);
+  if (!sg || !map || !oldid || !total || !bad || !ask_d || !moved_d) return EVM_ENOMEM;
+  HIPR(hipMemcpyAsync(sg, hs.data(), sizeof(LSeg) * ns, hipMemcpyHostToDevice, ctx->stream));
+  if (n_ask) HIPR(hipMemcpyAsync(ask_d, ask, sizeof(u64) * n_ask, hipMemcpyHostToDevice, ctx->stream));
+  HIPR(hipMemsetAsync(map, 0, sizeof(u64) * (M + 1), ctx->stream));
+  HIPR(hipMemsetAsync(total, 0, sizeof(u64), ctx->stream));
+  HIPR(hipMemsetAsync(bad, 0, sizeof(u32), ctx->stream));
+  // ---- mark, renumber
+  if (n) KLAUNCH(k_cmp_mark, dim3(grid_for(n, 256)), dim3(256), rows.id, n, M, map, bad);
+  int st = scan_exclusive<u64, OpAdd>(ctx, S, map, M, map, map + M);
+  if (st) return st;
+  KLAUNCH(k_cmp_rows, dim3(grid_for(M, 256)), dim3(256), sg, ns, map, M, n, oldid, total);
+  u32 hb = 0;
+  u64 CB = 0;
+  {
+    LandList l;
+    l.add(bad, &hb, sizeof(u32));
+    l.add(total, &CB, sizeof(u64));
+    if ((st = land_words(ctx, l))) return st;
+  }
+  if (hb) return EVM_ESTATE;  // (a store id outside the log, or held by two rows)
+  // ---- gather into one new segment
+  SyncSeg g{};
+  if (n) {
+    if ((st = seg_alloc(s, n, CB, &g))) return st;
+    g.base = 0;
+    KLAUNCH(k_cmp_len, dim3(grid_for(n, 256)), dim3(256), sg, ns, oldid, n, g.coff);
+    st = scan_exclusive<u64, OpAdd>(ctx, S, g.coff, n, g.coff, g.coff + n);
+    if (!st) {
+      KLAUNCH(k_cmp_ts, dim3(grid_for(3 * n, 256)), dim3(256), sg, ns, oldid, n, reinterpret_cast<uint4*>(g.ts));
+      if (CB)
+        KLAUNCH(k_cmp_content, dim3(grid_for((CB + 15) / 16, 256)), dim3(256), sg, ns, oldid, g.coff, n, CB,
+                reinterpret_cast<uint4*>(g.content));
+      st = hip_ok(hipStreamSynchronize(ctx->stream));
+    }
+    if (st) {
+      block_free(ctx, g.block, g.bytes);
+      return st;
+    }
+  }
+  // ---- commit: the store's ids, the segment list, the id space
+  if (n) KLAUNCH(k_cmp_remap, dim3(grid_for(n, 256)), dim3(256), rows.id, n, map);
+  if (n_ask) {
+    KLAUNCH(k_cmp_moved, dim3(grid_for(n_ask, 256)), dim3(256), ask_d, n_ask, map, M, moved_d);
+    HIPR(hipMemcpyAsync(moved_to, moved_d, sizeof(u64) * n_ask, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  st = hip_ok(hipStreamSynchronize(ctx->stream));
+  for (auto& o : s->segs) block_free(ctx, o.block, o.bytes);
+  s->segs.clear();
+  if (n) s->segs.push_back(g);
+  s->next_id = n;
+  return st;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The snapshot file being written: sections in order, each summed as its
+// bytes pass; the header goes in last (over the placeholder).
+struct SnapOut {
+  FILE* f = nullptr;
+  SnapHeader h;
+  int sec = -1;
+  Sum64 sum;
+  u64 put_bytes = 0;
+  void begin(int k) {
+    sec = k;
+    sum = Sum64();
+    put_bytes = 0;
+  }
+  int put(const void* p, size_t n) {
+    if (!n) return EVM_OK;
+    sum.update(p, n);
+    put_bytes += n;
+    return fwrite(p, 1, n, f) == n ? EVM_OK : EVM_EINVAL;
+  }
+  int end() {
+    h.sum[sec] = sum.digest();
+    return put_bytes == h.len[sec] ? EVM_OK : EVM_ESTATE;
+  }
+};
+
+int save_file(evm_sync_server* s, FILE* f, const uint8_t* blob, u64 blob_len) {
+  evm_ctx* ctx = s->ctx;
+  StoreRows rows;
+  store_rows(s->store, &rows);
+  const u64 n = rows.n;
+  const u32 U = s->users;
+  const SyncSeg* g = s->segs.empty() ? nullptr : &s->segs[0];
+  Scratch S(ctx);
+  int st;
+  // the small sections to the host; each row's owner slot
+  std::vector<u32> klen(U);
+  std::vector<uint8_t> keys(s->kused), flag(U);
+  u32* owner = S.alloc<u32>(n);
+  u32* bad = S.alloc<u32>(1);
+  if (!owner || !bad) return EVM_ENOMEM;
+  if (U) {
+    HIPR(hipMemcpyAsync(klen.data(), s->klen, sizeof(u32) * U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPR(hipMemcpyAsync(flag.data(), s->flag, U, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (s->kused) HIPR(hipMemcpyAsync(keys.data(), s->kbytes, s->kused, hipMemcpyDeviceToHost, ctx->stream));
+  HIPR(hipMemsetAsync(bad, 0, sizeof(u32), ctx->stream));
+  if (n) KLAUNCH(k_snap_owner, dim3(grid_for(n, 256)), dim3(256), rows.owner, rows.id, n, owner, bad);
+  u32 hb = 0;
+  HIPR(hipMemcpyAsync(&hb, bad, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIPR(hipStreamSynchronize(ctx->stream));
+  if (hb) return EVM_ESTATE;
+  std::vector<int32_t> root(std::max<u32>(s->cap, 1));
+  std::vector<uint8_t> present(std::max<u32>(s->cap, 1));
+  if ((st = evm_tree_roots(ctx, evm_store_tree(s->store), root.data(), present.data()))) return st;
+  for (u32 o = U; o < s->cap; ++o)
+    if (present[o]) return EVM_ESTATE;  // (rows of an owner the directory does not know)
+  SnapOut w;
+  w.f = f;
+  w.h.users = U;
+  w.h.rows = n;
+  w.h.content_bytes = g ? g->cb : 0;
+  w.h.key_bytes = s->kused;
+  w.h.blob_bytes = blob_len;
+  snap_lengths(&w.h);
+  uint8_t hdr[SNAP_HEADER_BYTES] = {};
+  if (fwrite(hdr, 1, SNAP_HEADER_BYTES, f) != SNAP_HEADER_BYTES) return EVM_EINVAL;
+  auto host_section = [&](int k, const void* p, size_t bytes) -> int {
+    w.begin(k);
+    int e = w.put(p, bytes);
+    return e ? e : w.end();
+  };
+  auto dev_section = [&](int k, const void* p, size_t bytes) -> int {
+    w.begin(k);
+    int e = bytes ? stage_d2h_each(ctx, p, bytes, [&](const uint8_t* q, size_t m) { return w.put(q, m); }) : EVM_OK;
+    return e ? e : w.end();
+  };
+  std::vector<uint8_t> le(std::max<size_t>((size_t)U * 5, 8));
+  for (u32 k = 0; k < U; ++k)
+    for (int b = 0; b < 4; ++b) le[(size_t)k * 4 + b] = (uint8_t)(klen[k] >> (8 * b));
+  if ((st = host_section(SN_KLEN, le.data(), (size_t)U * 4))) return st;
+  if ((st = host_section(SN_KEYS, keys.data(), keys.size()))) return st;
+  if ((st = host_section(SN_FLAGS, flag.data(), U))) return st;
+  // (the device's arrays are little-endian words already)
+  if ((st = dev_section(SN_OWNER, owner, n * 4))) return st;
+  if ((st = dev_section(SN_TS, g ? g->ts : nullptr, n * 48))) return st;
+  if (g) {
+    if ((st = dev_section(SN_COFF, g->coff, (n + 1) * 8))) return st;
+  } else {
+    const uint8_t zero[8] = {};
+    if ((st = host_section(SN_COFF, zero, 8))) return st;
+  }
+  if ((st = dev_section(SN_CONTENT, g ? g->content : nullptr, w.h.content_bytes))) return st;
+  for (u32 k = 0; k < U; ++k) {
+    for (int b = 0; b < 4; ++b) le[(size_t)k * 4 + b] = (uint8_t)((uint32_t)root[k] >> (8 * b));
+    le[(size_t)U * 4 + k] = present[k] ? 1 : 0;
+  }
+  if ((st = host_section(SN_ROOTS, le.data(), (size_t)U * 5))) return st;
+  if ((st = host_section(SN_BLOB, blob, blob_len))) return st;
+  snap_header_write(w.h, hdr);
+  if (fseek(f, 0, SEEK_SET) != 0 || fwrite(hdr, 1, SNAP_HEADER_BYTES, f) != SNAP_HEADER_BYTES) return EVM_EINVAL;
+  if (fflush(f) != 0 || fsync(fileno(f)) != 0) return EVM_EINVAL;
+  return EVM_OK;
+}
+
+// one section of the (verified) file, through the staging ring to the device
+int load_section(evm_ctx* ctx, FILE* f, const SnapHeader& h, int k, void* dst) {
+  if (!h.len[k]) return EVM_OK;
+  if (fseek(f, (long)h.at(k), SEEK_SET) != 0) return EVM_ESNAPSHOT;
+  return stage_h2d_each(ctx, dst, h.len[k],
+                        [&](uint8_t* p, size_t m) { return fread(p, 1, m, f) == m ? EVM_OK : EVM_ESNAPSHOT; });
+}
+int load_host(FILE* f, const SnapHeader& h, int k, void* dst) {
+  if (!h.len[k]) return EVM_OK;
+  if (fseek(f, (long)h.at(k), SEEK_SET) != 0) return EVM_ESNAPSHOT;
+  return fread(dst, 1, h.len[k], f) == h.len[k] ? EVM_OK : EVM_ESNAPSHOT;
+}
+
+int load_file(evm_ctx* ctx, evm_sync_server* s, FILE* f, const SnapHeader& h) {
+  int st;
+  const u32 U = (u32)h.users;
+  const u64 n = h.rows;
+  // ---- the users, in slot order (the directory's insert path)
+  if (U) {
+    std::vector<uint8_t> le(h.len[SN_KLEN]), keys(std::max<u64>(h.key_bytes, 1)), flag(U);
+    if ((st = load_host(f, h, SN_KLEN, le.data()))) return st;
+    if ((st = load_host(f, h, SN_KEYS, keys.data()))) return st;
+    if ((st = load_host(f, h, SN_FLAGS, flag.data()))) return st;
+    std::vector<uint64_t> koff((size_t)U + 1, 0);
+    for (u32 k = 0; k < U; ++k) {
+      u32 L = 0;
+      for (int b = 3; b >= 0; --b) L = (L << 8) | le[(size_t)k * 4 + b];
+      koff[k + 1] = koff[k] + L;
+    }
+    std::vector<uint32_t> slots(U);
+    st = evm_sync_users(s, keys.data(), koff.data(), U, 1, slots.data());
+    if (st == EVM_EROUNDS) return EVM_ESNAPSHOT;  // (one userId twice)
+    if (st) return st;
+    for (u32 k = 0; k < U; ++k)
+      if (slots[k] != k) return EVM_ESNAPSHOT;
+    HIPR(hipMemcpyAsync(s->flag, flag.data(), U, hipMemcpyHostToDevice, ctx->stream));
+    HIPR(hipStreamSynchronize(ctx->stream));
+  }
+  Scratch S(ctx);
+  u32* bad = S.alloc<u32>(1);
+  if (!bad) return EVM_ENOMEM;
+  HIPR(hipMemsetAsync(bad, 0, sizeof(u32), ctx->stream));
+  // ---- the rows: the log's one segment, ingested in id order from id 0
+  if (n) {
+    u32* owner = S.alloc<u32>(n);
+    uint8_t* flags = S.alloc<uint8_t>(n);
+    if (!owner || !flags) return EVM_ENOMEM;
+    SyncSeg g;
+    if ((st = seg_alloc(s, n, h.content_bytes, &g))) return st;
+    st = load_section(ctx, f, h, SN_OWNER, owner);
+    if (!st) st = load_section(ctx, f, h, SN_TS, g.ts);
+    if (!st) st = load_section(ctx, f, h, SN_COFF, g.coff);
+    if (!st) st = load_section(ctx, f, h, SN_CONTENT, g.content);
+    if (!st) {
+      st = evm_server_ingest(ctx, s->store, reinterpret_cast<const char*>(g.ts), 48, n, owner, 0, flags);
+      if (st == EVM_ENONCANON || st == EVM_EINVAL) st = EVM_ESNAPSHOT;  // (rows no save could have written)
+    }
+    if (st) {
+      (void)hipStreamSynchronize(ctx->stream);
+      block_free(ctx, g.block, g.bytes);
+      return st;
+    }
+    s->segs.push_back(g);
+    s->next_id = n;
+    KLAUNCH(k_snap_all_ins, dim3(grid_for(n, 256)), dim3(256), flags, n, bad);
+  }
+  // ---- the rebuilt roots against the saved ones, on the device
+  const u32 O = s->cap;
+  if (O) {
+    std::vector<uint8_t> le(std::max<size_t>((size_t)U * 5, 1));
+    if ((st = load_host(f, h, SN_ROOTS, le.data()))) return st;
+    std::vector<int32_t> wr(std::max<u32>(U, 1));
+    for (u32 k = 0; k < U; ++k) {
+      u32 v = 0;
+      for (int b = 3; b >= 0; --b) v = (v << 8) | le[(size_t)k * 4 + b];
+      wr[k] = (int32_t)v;
+    }
+    int32_t* root = S.alloc<int32_t>(O);
+    uint8_t* present = S.alloc<uint8_t>(O);
+    int32_t* want_r = S.alloc<int32_t>(U);
+    uint8_t* want_p = S.alloc<uint8_t>(U);
+    if (!root || !present || !want_r || !want_p) return EVM_ENOMEM;
+    if (U) {
+      HIPR(hipMemcpyAsync(want_r, wr.data(), sizeof(int32_t) * U, hipMemcpyHostToDevice, ctx->stream));
+      HIPR(hipMemcpyAsync(want_p, le.data() + (size_t)U * 4, U, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((st = tree_roots_dev(ctx, evm_store_tree(s->store), root, present))) return st;
+    KLAUNCH(k_snap_roots, dim3(grid_for(O, 256)), dim3(256), root, present, O, want_r, want_p, U, bad);
+  }
+  u32 hb = 0;
+  HIPR(hipMemcpyAsync(&hb, bad, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIPR(hipStreamSynchronize(ctx->stream));
+  return hb ? EVM_ESNAPSHOT : EVM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int evm_sync_save(evm_sync_server* s, const char* path, const uint8_t* blob, uint64_t blob_len) {
+  if (!s || !path || !*path || (blob_len && !blob)) return EVM_EINVAL;
+  uint64_t nm = 0;
+  evm_store_info(s->store, nullptr, &nm);
+  if (s->segs.size() > 1 || s->next_id != nm || (s->segs.size() == 1 && s->segs[0].n != nm)) return EVM_ESTATE;
+  const std::string tmp = std::string(path) + ".tmp";
+  FILE* f = fopen(tmp.c_str(), "wb");
+  if (!f) return EVM_EINVAL;
+  int st = save_file(s, f, blob, blob_len);
+  if (fclose(f) != 0 && !st) st = EVM_EINVAL;
+  if (!st && rename(tmp.c_str(), path) != 0) st = EVM_EINVAL;
+  if (st) (void)remove(tmp.c_str());
+  return st;
+}
+
+int evm_sync_load(evm_ctx* ctx, evm_store* store, const char* path, evm_sync_server** out, uint8_t* blob,
+                  uint64_t blob_cap, uint64_t* blob_len) {
+  if (!ctx || !store || !path || !out || !blob_len || (blob_cap && !blob)) return EVM_EINVAL;
+  *out = nullptr;
+  *blob_len = 0;
+  // ---- the whole file on the host first: nothing reaches the device before it holds
+  SnapHeader h;
+  int st = snap_verify(path, &h);
+  if (st) return st;
+  uint32_t O = 0;
+  uint64_t nm = 0;
+  if (evm_store_info(store, &O, &nm) || nm != 0) return EVM_EINVAL;
+  if (h.users > O) return EVM_ECAPACITY;
+  *blob_len = h.blob_bytes;
+  if (h.blob_bytes > blob_cap) return EVM_ECAPACITY;
+  FILE* f = fopen(path, "rb");
+  if (!f) return EVM_ESNAPSHOT;
+  evm_sync_server* s = nullptr;
+  st = evm_sync_create(ctx, store, &s);
+  if (!st) st = load_file(ctx, s, f, h);
+  if (!st) st = load_host(f, h, SN_BLOB, blob);
+  fclose(f);
+  if (st) {
+    if (s) evm_sync_destroy(s);
+    (void)store_reset(ctx, store);
+    return st;
+  }
+  *out = s;
+  return EVM_OK;
+}
 
 }  // extern "C"

@@ -74,8 +74,21 @@ REQUEST_KIND = _lib.PB_SYNC_REQUEST
 TIMING_PARTS = ("h2d", "decode", "users", "ingest", "trees", "select", "encode", "d2h")
 
 
+SNAPSHOT_BLOB_VERSION = 1  # the JSON SyncServer.save puts in the snapshot's blob
+
+
 def _np_ptr(a: np.ndarray):
     return C.c_void_p(a.ctypes.data)
+
+
+def snapshot_info(path: str) -> Dict[str, int]:
+    """A snapshot file verified on the host (evm_snapshot_info: header, lengths,
+    every checksum; no GPU) -> its counts.  EngineError(EVM_ESNAPSHOT) if it
+    is damaged, truncated or of an unknown version."""
+    info = _lib.SnapshotInfo()
+    check(_lib.load().evm_snapshot_info(path.encode(), C.byref(info)), "evm_snapshot_info")
+    return {"version": info.version, "users": info.users, "rows": info.rows,
+            "content_bytes": info.content_bytes, "blob_bytes": info.blob_bytes}
 
 
 _HEX = set(b"0123456789abcdefABCDEF")
@@ -243,13 +256,16 @@ class SyncServer:
     a native round (evm_sync_*) that owns the user directory and the message
     log."""
 
-    def __init__(self, eng: Engine, capacity: int):
+    def __init__(self, eng: Engine, capacity: int, _loaded=None):
         self.eng = eng
-        self.store = eng.store_new(capacity)
-        self.capacity = capacity
         lib = _lib.load()
-        h = C.c_void_p()
-        check(lib.evm_sync_create(eng.h, self.store.h, C.byref(h)), "evm_sync_create")
+        if _loaded is None:
+            self.store = eng.store_new(capacity)
+            h = C.c_void_p()
+            check(lib.evm_sync_create(eng.h, self.store.h, C.byref(h)), "evm_sync_create")
+        else:
+            self.store, h = _loaded  # (SyncServer.load: the store rebuilt from a snapshot and its native server)
+        self.capacity = capacity
         self.h = h
         self._rounds = 0  # native rounds run (a DeviceResponses is valid until the next)
         self._ok = None   # the last round's answered requests (bool array)
@@ -269,6 +285,85 @@ class SyncServer:
     def next_id(self) -> int:
         """The id the next stored message gets (ids are consecutive over rounds and per-request ingests)."""
         return int(_lib.load().evm_sync_next_id(self.h))
+
+    # ------------------------------------------- the log: compaction, save, load
+    def log_info(self) -> Dict[str, int]:
+        """The message log's shape: segments, rows (= next_id), content bytes."""
+        ns, nr, cb = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        check(_lib.load().evm_sync_log_info(self.h, C.byref(ns), C.byref(nr), C.byref(cb)), "evm_sync_log_info")
+        return {"segments": ns.value, "rows": nr.value, "content_bytes": cb.value}
+
+    def compact(self, ask: Sequence[int] = ()) -> List[Optional[int]]:
+        """The log reduced to the rows the store holds, in one segment
+        (evm_sync_compact): resent timestamps and the rows of requests that
+        committed nothing are dropped, message ids renumbered in order.  The
+        ids this server keeps for rows under lenient spellings follow; `ask`
+        (old ids the caller holds) -> their new ids (None: dropped)."""
+        held = sorted(set(self._raw) | {mid for rows in self.lenient.values() for _, mid in rows.values()})
+        want = np.asarray(held + [int(a) for a in ask], dtype=np.uint64)
+        moved = np.zeros(max(len(want), 1), dtype=np.uint64)
+        check(_lib.load().evm_sync_compact(self.h, _np_ptr(want) if len(want) else None, len(want), _np_ptr(moved)),
+              "evm_sync_compact")
+        gone = 0xFFFFFFFFFFFFFFFF
+        new = {old: int(m) for old, m in zip(held, moved[:len(held)].tolist())}
+        if any(m == gone for m in new.values()):
+            raise RuntimeError("SyncServer.compact: a row kept under a lenient spelling is not in the store")
+        self._raw = {new[mid]: raw for mid, raw in self._raw.items()}
+        self.lenient = {u: {canon: (raw, new[mid]) for canon, (raw, mid) in rows.items()}
+                        for u, rows in self.lenient.items()}
+        return [None if m == gone else int(m) for m in moved[len(held):len(want)].tolist()]
+
+    def save(self, path: str):
+        """The server written to `path` (evm_sync_save; compacts first): the
+        directory, the hand-over flags, the stored rows and contents, the
+        owners' roots, and this class's own state (_raw, lenient, detached)
+        as JSON in the file's blob.  Two saves of one state are byte-equal."""
+        import json
+
+        self.compact()
+        blob = json.dumps({"version": SNAPSHOT_BLOB_VERSION,
+                           "raw": {str(mid): raw for mid, raw in self._raw.items()},
+                           "lenient": {u: {canon: [raw, mid] for canon, (raw, mid) in rows.items()}
+                                       for u, rows in self.lenient.items()},
+                           "detached": sorted(self.detached)},
+                          sort_keys=True, separators=(",", ":")).encode("utf-8")
+        b = np.frombuffer(blob, dtype=np.uint8)
+        check(_lib.load().evm_sync_save(self.h, path.encode(), _np_ptr(b), len(b)), "evm_sync_save")
+
+    @classmethod
+    def load(cls, eng: Engine, path: str, capacity: Optional[int] = None) -> "SyncServer":
+        """A server read back from save()'s file (evm_sync_load) into a new
+        store of `capacity` owner slots (default: the snapshot's users; more
+        lets new users in).  Slots, flags, message ids, trees and the
+        lenient-spelling state are the saved server's; the file is verified
+        on the host first (EngineError with EVM_ESNAPSHOT if it is damaged)."""
+        import json
+
+        lib = _lib.load()
+        cap = max(snapshot_info(path)["users"], 1) if capacity is None else capacity
+        store = eng.store_new(cap)
+        h, n = C.c_void_p(), C.c_uint64()
+        blob = np.zeros(1 << 16, dtype=np.uint8)
+        st = lib.evm_sync_load(eng.h, store.h, path.encode(), C.byref(h), _np_ptr(blob), len(blob), C.byref(n))
+        if st == _lib.EVM_ECAPACITY and n.value > len(blob):  # (a larger blob: nothing was loaded)
+            blob = np.zeros(n.value, dtype=np.uint8)
+            st = lib.evm_sync_load(eng.h, store.h, path.encode(), C.byref(h), _np_ptr(blob), len(blob), C.byref(n))
+        if st:
+            store.free()
+            raise _lib.EngineError(st, "evm_sync_load")
+        srv = cls(eng, cap, _loaded=(store, h))
+        try:
+            d = json.loads(blob[:n.value].tobytes().decode("utf-8"))
+            if d.get("version") != SNAPSHOT_BLOB_VERSION:
+                raise ValueError("blob version %r" % d.get("version"))
+            srv._raw = {int(mid): raw for mid, raw in d["raw"].items()}
+            srv.lenient = {u: {canon: (raw, int(mid)) for canon, (raw, mid) in rows.items()}
+                           for u, rows in d["lenient"].items()}
+            srv.detached = set(d["detached"])
+        except (ValueError, KeyError, TypeError) as e:
+            srv.close()
+            raise _lib.EngineError(_lib.EVM_ESNAPSHOT, "SyncServer.load: the blob is not this class's (%s)" % e)
+        return srv
 
     @property
     def slot(self) -> Dict[str, int]:
@@ -705,4 +800,4 @@ class SyncServer:
         return [(t, c) for t, c, _ in keep]
 
 
-__all__ = ["SyncServer", "ParseBodyError", "RangeError", "HandedOver"]
+__all__ = ["SyncServer", "ParseBodyError", "RangeError", "HandedOver", "snapshot_info"]

@@ -56,8 +56,10 @@ enum evm_status {
   EVM_EDIST = 9,      /* RCCL missing or a collective failed (evm_dist_*) */
   EVM_ESTATE = 10,    /* a store invariant broke in a merge (stored and new keys not disjoint); nothing committed */
   EVM_EROUNDS = 11,   /* evm_sync_round: a userId in two requests of one call; nothing applied (split the call) */
-  EVM_EHANDOVER = 12  /* evm_sync_round, per request: not modelled here (a nodeId that is not 16 hex chars, or a
+  EVM_EHANDOVER = 12, /* evm_sync_round, per request: not modelled here (a nodeId that is not 16 hex chars, or a
                          user handed to the caller); nothing of it applied -- the caller's reference path runs it */
+  EVM_ESNAPSHOT = 13  /* evm_sync_load / evm_snapshot_info: the file is damaged, truncated or of an unknown
+                         version, or the store rebuilt from it does not have the saved roots; nothing loaded */
 };
 
 /* ---- packed timestamp record (32 bytes, device) -------------------------
@@ -550,6 +552,62 @@ uint64_t evm_sync_next_id(const evm_sync_server* s);
 /* the last round's wall time by part, ms[8]: staging in (host rounds), decode,
  * users, addMessages, client trees, getMessages, encode, staging out (fetch) */
 int evm_sync_timing(const evm_sync_server* s, double* ms);
+
+/* The message log's shape: segments, rows (= evm_sync_next_id), content bytes
+ * (any pointer may be NULL).  Every round and every evm_sync_log_add appends
+ * one segment holding every row it was given, stored or not. */
+int evm_sync_log_info(const evm_sync_server* s, uint32_t* n_segments, uint64_t* n_rows, uint64_t* content_bytes);
+
+/* The log reduced to the rows the store holds, in ONE segment, on the device.
+ * The reference keeps exactly these: INSERT OR IGNORE stores a (timestamp,
+ * userId) once and a rolled-back request stores nothing (index.ts:64-75 the
+ * "message" table, :147-164 the transaction).  A live row's new id is its
+ * rank among the live old ids, so arrival order is kept; the store's ids are
+ * rewritten, evm_sync_next_id becomes the store's message count.  ask (host,
+ * n_ask old ids, may be NULL) -> moved_to (host): each id's new id, or
+ * UINT64_MAX for a row that was dropped (or never existed).
+ * Everything is allocated before anything changes: EVM_ENOMEM leaves the
+ * server as it was, and so does EVM_ESTATE (a store id outside the log, or
+ * held twice).  Peak device memory: the old log + the new log + 8 B per old
+ * id (the id map) + 8 B per live row (each new row's old id; scratch).
+ * Responses of the last round stay valid; ids a caller holds do not. */
+int evm_sync_compact(evm_sync_server* s, const uint64_t* ask, uint64_t n_ask, uint64_t* moved_to);
+
+/* The server written to one file and read back: what the reference keeps in
+ * db.sqlite across a restart (index.ts:64-75 the schema, :147-164 each
+ * committed transaction).  The file is little-endian, holds no pointers,
+ * times or capacities (two saves of one state are byte-identical), carries a
+ * 64-bit checksum per section, and is written as path + ".tmp", fsynced and
+ * renamed.  blob: the caller's opaque bytes, returned by the load.
+ *
+ * evm_sync_save needs a compact log (one segment at most, as many rows as the
+ * store has messages: call evm_sync_compact first), else EVM_ESTATE; a file
+ * that cannot be created, written or renamed answers EVM_EINVAL (no file and
+ * no ".tmp" is left).
+ *
+ * evm_sync_load makes a new server over `store`, which must be empty
+ * (EVM_EINVAL) with at least the snapshot's users as owners (EVM_ECAPACITY;
+ * more is fine).  The whole file is verified on the host before anything
+ * reaches the device: a damaged, truncated or unknown-version file answers
+ * EVM_ESNAPSHOT with the store untouched.  The store is then rebuilt by
+ * evm_server_ingest of the saved rows (ids come back as saved) and its
+ * per-owner roots compared with the saved ones; a mismatch answers
+ * EVM_ESNAPSHOT too, the store emptied again.  blob_cap smaller than the
+ * saved blob: EVM_ECAPACITY with *blob_len set (nothing loaded).
+ *
+ * evm_snapshot_info verifies a file the same way and reports its counts; it
+ * needs no context and no GPU. */
+struct evm_snapshot_info {
+  uint32_t version;
+  uint64_t users;
+  uint64_t rows;
+  uint64_t content_bytes;
+  uint64_t blob_bytes;
+};
+int evm_sync_save(evm_sync_server* s, const char* path, const uint8_t* blob, uint64_t blob_len);
+int evm_sync_load(evm_ctx* ctx, evm_store* store, const char* path, evm_sync_server** out, uint8_t* blob,
+                  uint64_t blob_cap, uint64_t* blob_len);
+int evm_snapshot_info(const char* path, struct evm_snapshot_info* out);
 
 /* ------------------------------------------------------------------------
  * Multi-GPU owner sharding (evm_dist.hip).  One process per

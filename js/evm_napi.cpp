@@ -1336,6 +1336,80 @@ napi_value SyncUserFlag(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+std::string string_of(napi_env env, napi_value v) {
+  size_t len = 0;
+  napi_get_value_string_utf8(env, v, nullptr, 0, &len);
+  std::string s(len + 1, '\0');
+  napi_get_value_string_utf8(env, v, &s[0], len + 1, &len);
+  s.resize(len);
+  return s;
+}
+
+// syncCompact(ctx, server): the message log reduced to the stored rows, one segment (evm_sync_compact)
+napi_value SyncCompact(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return nullptr;
+  Ctx* cx = ctx_of(env, a[0]);
+  std::lock_guard<std::mutex> lock(cx->m);
+  const int st = evm_sync_compact((evm_sync_server*)ext(env, a[1]), nullptr, 0, nullptr);
+  if (st) return throw_status(env, st, "evm_sync_compact");
+  return nullptr;
+}
+
+// syncSave(ctx, server, path): compacts, then writes the snapshot file (evm_sync_save; no blob)
+napi_value SyncSave(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return nullptr;
+  Ctx* cx = ctx_of(env, a[0]);
+  std::lock_guard<std::mutex> lock(cx->m);
+  evm_sync_server* srv = (evm_sync_server*)ext(env, a[1]);
+  const std::string path = string_of(env, a[2]);
+  int st = evm_sync_compact(srv, nullptr, 0, nullptr);
+  if (st) return throw_status(env, st, "evm_sync_compact");
+  st = evm_sync_save(srv, path.c_str(), nullptr, 0);
+  if (st) return throw_status(env, st, "evm_sync_save");
+  return nullptr;
+}
+
+// syncLoad(ctx, store, path) -> server handle over the (empty) store, rebuilt from the file (evm_sync_load)
+napi_value SyncLoad(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return nullptr;
+  Ctx* cx = ctx_of(env, a[0]);
+  std::lock_guard<std::mutex> lock(cx->m);
+  const std::string path = string_of(env, a[2]);
+  struct evm_snapshot_info si;
+  int st = evm_snapshot_info(path.c_str(), &si);
+  if (st) return throw_status(env, st, "evm_snapshot_info");
+  std::vector<uint8_t> blob((size_t)si.blob_bytes + 1);  // (another binding's blob is read and dropped)
+  uint64_t blob_len = 0;
+  evm_sync_server* s = nullptr;
+  st = evm_sync_load(cx->c, (evm_store*)ext(env, a[1]), path.c_str(), &s, blob.data(), blob.size(), &blob_len);
+  if (st) return throw_status(env, st, "evm_sync_load");
+  return make_ext(env, s);
+}
+
+// syncLogInfo(ctx, server) -> { segments, rows, contentBytes }
+napi_value SyncLogInfo(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return nullptr;
+  Ctx* cx = ctx_of(env, a[0]);
+  std::lock_guard<std::mutex> lock(cx->m);
+  uint32_t ns = 0;
+  uint64_t nr = 0, cb = 0;
+  const int st = evm_sync_log_info((evm_sync_server*)ext(env, a[1]), &ns, &nr, &cb);
+  if (st) return throw_status(env, st, "evm_sync_log_info");
+  napi_value out, v;
+  napi_create_object(env, &out);
+  napi_create_uint32(env, ns, &v);
+  napi_set_named_property(env, out, "segments", v);
+  napi_create_double(env, (double)nr, &v);
+  napi_set_named_property(env, out, "rows", v);
+  napi_create_double(env, (double)cb, &v);
+  napi_set_named_property(env, out, "contentBytes", v);
+  return out;
+}
+
 napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char* name;
@@ -1354,7 +1428,8 @@ napi_value Init(napi_env env, napi_value exports) {
              {"distInitLoopback", DistInitLoopback}, {"distDirectory", DistDirectory},
              {"distHotOwners", DistHotOwners}, {"distSplit", DistSplit},   {"distSelectSplit", DistSelectSplit},
              {"distSplitApply", DistSplitApply}, {"syncCreate", SyncCreate}, {"syncDestroy", SyncDestroy},
-             {"syncRound", SyncRound},       {"syncUserFlag", SyncUserFlag}};
+             {"syncRound", SyncRound},       {"syncUserFlag", SyncUserFlag}, {"syncCompact", SyncCompact},
+             {"syncSave", SyncSave},         {"syncLoad", SyncLoad},         {"syncLogInfo", SyncLogInfo}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -303,10 +303,37 @@ const EVM_EROUNDS = 11;
 const SYNC_ANSWERED = 0;
 const SYNC_500 = new Set([1 /* EVM_EINVAL */, 4 /* EVM_ERANGE */, 5 /* EVM_ETREE */]);
 class SyncServer {
-  constructor(engine, nUsers) {
+  constructor(engine, nUsers, loaded = null) {
     this.engine = engine;
-    this.store = addon.storeNew(engine.ctx, nUsers);
-    this.h = addon.syncCreate(engine.ctx, this.store);
+    this.store = loaded ? loaded.store : addon.storeNew(engine.ctx, nUsers);
+    this.h = loaded ? loaded.h : addon.syncCreate(engine.ctx, this.store);
+  }
+  // A server read back from save()'s file into a new store of nUsers owner
+  // slots (at least the saved users; more lets new users in): the state
+  // db.sqlite keeps across a restart (index.ts:64-75, :147-164).  Throws
+  // (status 13) if the file is damaged; nothing is loaded then.
+  static load(engine, path, nUsers) {
+    const store = addon.storeNew(engine.ctx, nUsers);
+    let h;
+    try {
+      h = addon.syncLoad(engine.ctx, store, path);
+    } catch (e) {
+      addon.storeFree(engine.ctx, store);
+      throw e;
+    }
+    return new SyncServer(engine, nUsers, { store, h });
+  }
+  // the message log reduced to the stored rows, in one segment
+  compact() {
+    addon.syncCompact(this.engine.ctx, this.h);
+  }
+  // compacts, then writes the server to path (path + ".tmp", fsync, rename)
+  save(path) {
+    addon.syncSave(this.engine.ctx, this.h, path);
+  }
+  // { segments, rows, contentBytes } of the message log
+  logInfo() {
+    return addon.syncLogInfo(this.engine.ctx, this.h);
   }
   close() {
     addon.syncDestroy(this.engine.ctx, this.h);
