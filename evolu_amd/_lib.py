@@ -25,6 +25,12 @@ EVM_ESTATE = 10
 EVM_EROUNDS = 11
 EVM_EHANDOVER = 12
 EVM_ESNAPSHOT = 13
+EVM_EDATE = 14  # evm_sync_round with SYNC_OPT_DATE_500: an invalid date -> 500, nothing stored
+TS_OK = 0  # evm_ts_classify
+TS_RANGE_ERROR = 1
+TS_UNSUPPORTED = 2
+SYNC_OPT_DATE_500 = 1  # evm_sync_set_option
+SYNC_OPT_HANDOVER = 2
 SYNC_HOST = 0
 SYNC_DEVICE = 1
 DIST_ID_BYTES = 128
@@ -84,6 +90,7 @@ SIGNATURES = {
     "evm_copy_h2d": (_i, [_vp, _vp, _vp, _sz]),
     "evm_copy_d2h": (_i, [_vp, _vp, _vp, _sz]),
     "evm_pack": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "evm_ts_classify": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "evm_tree_new": (_i, [_vp, _u32, C.POINTER(_vp)]),
     "evm_tree_from_leaves": (_i, [_vp, _u32, _vp, _vp, _vp, C.POINTER(_vp)]),
     "evm_tree_free": (_i, [_vp, _vp]),
@@ -127,8 +134,11 @@ SIGNATURES = {
     "evm_sync_round": (_i, [_vp, _vp, _vp, _u32, _i, _vp, _vp, C.POINTER(C.c_uint64)]),
     "evm_sync_fetch": (_i, [_vp, _vp]),
     "evm_sync_responses_dev": (_vp, [_vp]),
+    "evm_sync_set_option": (_i, [_vp, _i, C.c_int64]),
+    "evm_sync_export": (_i, [_vp, _vp, _u32, _vp, C.POINTER(C.c_uint64)]),
     "evm_sync_users": (_i, [_vp, _vp, _vp, _u32, _i, _vp]),
     "evm_sync_user_flag": (_i, [_vp, _u32, _i]),
+    "evm_sync_user_flag_get": (_i, [_vp, _u32, C.POINTER(_i)]),
     "evm_sync_user_count": (_i, [_vp, C.POINTER(_u32), C.POINTER(C.c_uint64)]),
     "evm_sync_user_keys": (_i, [_vp, _vp, _vp]),
     "evm_sync_log_add": (_i, [_vp, _vp, _sz, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
@@ -143,6 +153,7 @@ SIGNATURES = {
     "evm_store_since": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "evm_server_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "evm_store_select_after": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "evm_store_select_all": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "evm_dist_unique_id": (_i, [_vp]),
     "evm_dist_init": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
     "evm_dist_free": (None, [_vp, _vp]),

@@ -19,6 +19,7 @@
 #include "evm_device.hpp"
 #include "evm_internal.hpp"
 #include "evm_prims.hpp"
+#include "evm_tsclass.hpp"
 
 using namespace evm;
 
@@ -95,6 +96,24 @@ __global__ void k_rf_next(const u64* __restrict__ T, const u64* __restrict__ E, 
   if (threadIdx.x == 0 && out->first_err != ~0ull) {
     const size_t i = out->first_err >> 2;
     out->err_next = max(max(P.m0, E[i]), T[i]);
+  }
+}
+
+// evm_ts_classify: one row per lane.  The rows lie at any byte alignment and
+// nothing past a row's 46 bytes is read: byte loads into registers.
+__global__ void k_ts_classify(const uint8_t* __restrict__ ts, size_t stride, size_t n, uint8_t* __restrict__ cls,
+                              uint8_t* __restrict__ canon) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    uint8_t r[46], c[46];
+    const uint8_t* p = ts + i * stride;
+#pragma unroll
+    for (int k = 0; k < 46; ++k) r[k] = p[k];
+    const uint8_t v = ts_classify(r, canon ? c : nullptr);
+    cls[i] = v;
+    if (canon && v == TS_OK) {
+#pragma unroll
+      for (int k = 0; k < 46; ++k) canon[i * 46 + k] = c[k];
+    }
   }
 }
 
@@ -180,4 +199,15 @@ extern "C" int evm_receive_fold(evm_ctx* ctx, const char* ts, size_t stride, siz
     res->counter = (uint32_t)ho.counter;
   }
   return EVM_OK;
+}
+
+static_assert(EVM_TS_OK == TS_OK && EVM_TS_RANGE_ERROR == TS_RANGE_ERROR && EVM_TS_UNSUPPORTED == TS_UNSUPPORTED,
+              "evm.h and evm_tsclass.hpp name the same classes");
+
+extern "C" int evm_ts_classify(evm_ctx* ctx, const char* ts, size_t stride, size_t n, uint8_t* cls, uint8_t* canon) {
+  if (!ctx || stride < 46 || (n && (!ts || !cls))) return EVM_EINVAL;
+  if (n == 0) return EVM_OK;
+  KLAUNCH(k_ts_classify, dim3(grid_for(n, 256)), dim3(256), reinterpret_cast<const uint8_t*>(ts), stride, n, cls,
+          canon);
+  return evm_sync(ctx);
 }

@@ -1043,6 +1043,7 @@ const char* evm_strerror(int s) {
     case EVM_EROUNDS: return "a userId in two requests of one call: split the call into rounds";
     case EVM_EHANDOVER: return "request not modelled here: the caller's reference path runs it";
     case EVM_ESNAPSHOT: return "snapshot file damaged, truncated, of an unknown version, or its roots do not match";
+    case EVM_EDATE: return "a timestamp whose date Date.parse rejects: toISOString throws a RangeError (500)";
   }
   return "unknown status";
 }

@@ -1886,6 +1886,16 @@ __global__ void k_sv_sel_first(StoreView st, u32 n_owners, const int64_t* __rest
   }
 }
 
+// evm_store_select_all's pass 1: every row of an active owner is a candidate
+__global__ void k_sv_sel_all(StoreView st, u32 n_owners, const uint8_t* __restrict__ active, u64* __restrict__ first,
+                             u32* __restrict__ cand) {
+  for (u32 o = blockIdx.x * blockDim.x + threadIdx.x; o < n_owners; o += gridDim.x * blockDim.x) {
+    const bool on = !active || active[o];
+    first[o] = on ? st.off[o] : 0;
+    cand[o] = on ? (u32)(st.off[o + 1] - st.off[o]) : 0u;
+  }
+}
+
 constexpr int SEL_THREADS = 256;
 
 // Owner of candidate j: the last owner whose candidate offset is <= j (owners
@@ -3449,7 +3459,7 @@ int evm::server_ingest_wire(evm_ctx* ctx, evm_store* s, const WireSrc& w, size_t
 // none), optionally excluding one node (server getMessages).
 static int select_after(evm_ctx* ctx, Scratch& S, const evm_store* s, const int64_t* bound, const char* node,
                         const uint8_t* active, uint64_t* sel_off, uint64_t* sel_id, uint64_t* sel_key, uint64_t cap,
-                        uint64_t* n_sel) {
+                        uint64_t* n_sel, bool all = false) {
   const u32 O = s->n_owners;
   int st;
   // candidate counts and their scans are u32: a store past 2^32 - 1 rows
@@ -3463,8 +3473,10 @@ static int select_after(evm_ctx* ctx, Scratch& S, const evm_store* s, const int6
   if (!first || !cand || !cpos || !req || !tot) return EVM_ENOMEM;
   HIPR(hipMemsetAsync(tot, 0, 2 * sizeof(u32), ctx->stream));
   const StoreView v = view_of(s);
-  KLAUNCH(k_sv_sel_first, dim3(grid_for(O, 64, 65536)), dim3(64), v, O, bound, (const uint8_t*)node, active, first,
-          cand, req, tot + 1);
+  if (all) KLAUNCH(k_sv_sel_all, dim3(grid_for(O, 256)), dim3(256), v, O, active, first, cand);
+  else
+    KLAUNCH(k_sv_sel_first, dim3(grid_for(O, 64, 65536)), dim3(64), v, O, bound, (const uint8_t*)node, active, first,
+            cand, req, tot + 1);
   if ((st = scan_exclusive<u32, OpAdd>(ctx, S, cand, O, cpos, cpos + O))) return st;
   u32 h[2];
   {
@@ -3567,6 +3579,17 @@ int evm_store_select_after(evm_ctx* ctx, const evm_store* s, const int64_t* boun
   }
   Scratch S(ctx);
   return select_after(ctx, S, s, bound, node, active, sel_off, sel_id, sel_key, cap, n_sel);
+}
+
+int evm_store_select_all(evm_ctx* ctx, const evm_store* s, const uint8_t* active, uint64_t* sel_off,
+                         uint64_t* sel_id, uint64_t cap, uint64_t* n_sel) {
+  if (!ctx || !s || !sel_off || !n_sel) return EVM_EINVAL;
+  if (s->n_owners == 0) {
+    *n_sel = 0;
+    return EVM_OK;
+  }
+  Scratch S(ctx);
+  return select_after(ctx, S, s, nullptr, nullptr, active, sel_off, sel_id, nullptr, cap, n_sel, true);
 }
 
 }  // extern "C"

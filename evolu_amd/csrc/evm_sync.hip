@@ -35,6 +35,7 @@
 #include "evm_internal.hpp"
 #include "evm_prims.hpp"
 #include "evm_snapshot.hpp"
+#include "evm_tsclass.hpp"
 
 using namespace evm;
 
@@ -290,6 +291,38 @@ __global__ void k_sync_answer(const u32* __restrict__ ans, u32 na, const u32* __
                               const int64_t* __restrict__ diff, uint8_t* __restrict__ skip) {
   for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < na; j += gridDim.x * blockDim.x)
     skip[j] = diff[slot[ans[j]]] == EVM_DIFF_RANGE_ERROR ? 1 : 0;
+}
+
+// EVM_SYNC_OPT_DATE_500: the rows the ingest flagged (only rejected owners
+// have any) classified one per lane; a RangeError row marks its request (the
+// last r with mb[r] <= i: requests outside the round have no rows)
+__global__ void k_sync_cls(const uint8_t* __restrict__ ts, u64 N, const uint8_t* __restrict__ flags,
+                           const u64* __restrict__ mb, u32 n, u32* __restrict__ rcls) {
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < N; i += (u64)gridDim.x * blockDim.x) {
+    if (!(flags[i] & EVM_MSG_BAD)) continue;
+    uint8_t row[46];
+    const uint8_t* p = ts + i * 48;
+#pragma unroll
+    for (int k = 0; k < 46; ++k) row[k] = p[k];
+    if (ts_classify(row, nullptr) != TS_RANGE_ERROR) continue;
+    u32 lo = 0, hi = n;  // mb[lo] <= i < mb[hi] (mb[0] = 0, mb[n] = N)
+    while (lo + 1 < hi) {
+      const u32 mid = (lo + hi) >> 1;
+      if (mb[mid] <= i) lo = mid;
+      else hi = mid;
+    }
+    atomicOr(&rcls[lo], 1u);
+  }
+}
+// EVM_SYNC_OPT_HANDOVER: the users of the requests answered EVM_ENONCANON
+__global__ void k_sync_hand(u32 n, const uint8_t* __restrict__ hand, const u32* __restrict__ slot, u32 users,
+                            uint8_t* __restrict__ flag) {
+  for (u32 r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x)
+    if (hand[r] && slot[r] < users) flag[slot[r]] = 1;
+}
+// evm_sync_export: the exported owners' mask for the selection
+__global__ void k_exp_active(const u32* __restrict__ owners, u32 n, uint8_t* __restrict__ active) {
+  for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) active[owners[j]] = 1;
 }
 
 // evm_sync_log_read: per id its segment row -> the 46-B timestamp and the
@@ -683,6 +716,8 @@ struct evm_sync_server {
   // messages are split and ingested on the context's stream
   hipStream_t ps = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // evm_sync_set_option (not state: a loaded server starts with both 0)
+  bool opt_date500 = false, opt_handover = false;
 };
 
 namespace {
@@ -1010,6 +1045,48 @@ int round_dev(evm_sync_server* sv, const uint8_t* arena, const u64* off_h, u32 n
       default: result[r] = EVM_ETREE; break;
     }
   }
+  // ---- the options: the rejected requests' rows classified (RangeError ->
+  // EVM_EDATE), the users of what stays EVM_ENONCANON handed over.  Nothing is
+  // launched for a round without such a request.
+  if (sv->opt_date500 || sv->opt_handover) {
+    bool rejected = false, noncanon = false;
+    for (u32 r = 0; r < n; ++r) {
+      noncanon = noncanon || result[r] == EVM_ENONCANON;
+      rejected = rejected || (incl[r] && result[r] == EVM_ENONCANON);
+    }
+    st = EVM_OK;
+    if (sv->opt_date500 && rejected) {  // (a rejected request has rows: N > 0, the round's segment is the last)
+      std::vector<u32> hcls(n);
+      u32* rcls = S.alloc<u32>(n);
+      if (!rcls) st = EVM_ENOMEM;
+      if (!st) st = hip_ok(hipMemsetAsync(rcls, 0, sizeof(u32) * n, ctx->stream));
+      if (!st) {
+        KLAUNCH(k_sync_cls, dim3(grid_for(N, 256)), dim3(256), sv->segs.back().ts, N, flags, mb_d, n, rcls);
+        st = hip_ok(hipMemcpyAsync(hcls.data(), rcls, sizeof(u32) * n, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (!st) st = hip_ok(hipStreamSynchronize(ctx->stream));
+      noncanon = false;
+      for (u32 r = 0; !st && r < n; ++r) {
+        if (incl[r] && result[r] == EVM_ENONCANON && (hcls[r] & 1u)) result[r] = EVM_EDATE;
+        noncanon = noncanon || result[r] == EVM_ENONCANON;
+      }
+    }
+    if (!st && sv->opt_handover && noncanon) {
+      std::vector<uint8_t> hand(n);
+      for (u32 r = 0; r < n; ++r) hand[r] = result[r] == EVM_ENONCANON;
+      uint8_t* hand_d = S.alloc<uint8_t>(n);
+      if (!hand_d) st = EVM_ENOMEM;
+      if (!st) st = hip_ok(hipMemcpyAsync(hand_d, hand.data(), n, hipMemcpyHostToDevice, ctx->stream));
+      if (!st) {
+        KLAUNCH(k_sync_hand, dim3(grid_for(n, 256)), dim3(256), n, hand_d, slot_d, sv->users, sv->flag);
+        st = hip_ok(hipStreamSynchronize(ctx->stream));  // (hand: host memory of this block)
+      }
+    }
+    if (st) {
+      free_client();
+      return st;
+    }
+  }
   const u32 na = (u32)ans.size();
   uint64_t nst = 0;
   evm_store_info(sv->store, nullptr, &nst);
@@ -1220,6 +1297,79 @@ int evm_sync_timing(const evm_sync_server* s, double* ms) {
 
 const uint8_t* evm_sync_responses_dev(const evm_sync_server* s) { return s ? s->resp : nullptr; }
 
+int evm_sync_set_option(evm_sync_server* s, int option, int64_t value) {
+  if (!s || (value != 0 && value != 1)) return EVM_EINVAL;
+  if (option == EVM_SYNC_OPT_DATE_500) s->opt_date500 = value != 0;
+  else if (option == EVM_SYNC_OPT_HANDOVER) s->opt_handover = value != 0;
+  else return EVM_EINVAL;
+  return EVM_OK;
+}
+
+int evm_sync_export(evm_sync_server* s, const uint32_t* slots, uint32_t n, uint64_t* resp_off, uint64_t* resp_bytes) {
+  if (!s || !resp_off || !resp_bytes || (n && !slots)) return EVM_EINVAL;
+  for (uint32_t k = 0; k < n; ++k)
+    if (slots[k] >= s->users) return EVM_EINVAL;
+  evm_ctx* ctx = s->ctx;
+  *resp_bytes = 0;
+  s->resp_used = 0;  // (the arena is rebuilt: the last round's responses are gone)
+  for (uint32_t k = 0; k <= n; ++k) resp_off[k] = 0;
+  if (!n) return EVM_OK;
+  int st;
+  const u32 O = s->cap;
+  uint64_t nst = 0;
+  evm_store_info(s->store, nullptr, &nst);
+  Scratch S(ctx);
+  u32* owners = S.alloc<u32>(n);
+  uint8_t* active = S.alloc<uint8_t>(O);
+  u64* sel_off = S.alloc<u64>((size_t)O + 1);
+  u64* sel_id = S.alloc<u64>(nst + 1);
+  u64* rout = S.alloc<u64>((size_t)n + 1);
+  if (!owners || !active || !sel_off || !sel_id || !rout) return EVM_ENOMEM;
+  HIPR(hipMemcpyAsync(owners, slots, sizeof(u32) * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPR(hipMemsetAsync(active, 0, O, ctx->stream));
+  KLAUNCH(k_exp_active, dim3(grid_for(n, 256)), dim3(256), owners, n, active);
+  // ---- SELECT timestamp, content ... WHERE userId = ? ORDER BY timestamp
+  uint64_t n_sel = 0;
+  if ((st = evm_store_select_all(ctx, s->store, active, U64P(sel_off), U64P(sel_id), nst + 1, &n_sel))) return st;
+  // ---- one SyncResponse per slot: the stored tree's text, the rows from the log
+  const u32 ns = (u32)s->segs.size();
+  std::vector<uint64_t> sbase(ns);
+  std::vector<const uint64_t*> srow(ns, nullptr), scoff(ns);
+  std::vector<const char*> sts(ns);
+  std::vector<const uint8_t*> scon(ns);
+  for (u32 k = 0; k < ns; ++k) {
+    sbase[k] = s->segs[k].base;
+    sts[k] = reinterpret_cast<const char*>(s->segs[k].ts);
+    scoff[k] = U64C(s->segs[k].coff);
+    scon[k] = s->segs[k].content;
+  }
+  uint64_t total = 0;
+  int ast = EVM_OK;
+  st = encode_responses_dev(
+      ctx, n, evm_store_tree(s->store), owners, U64C(sel_off), U64C(sel_id), nullptr, ns, sbase.data(), srow.data(),
+      sts.data(), 48, scoff.data(), scon.data(),
+      [&](uint64_t need) -> uint8_t* {
+        if (need + 16 > s->resp_bytes) {
+          if (s->resp) block_free(ctx, s->resp, s->resp_bytes);
+          size_t bytes = need + 16;
+          s->resp = static_cast<uint8_t*>(block_alloc(ctx, &bytes));
+          s->resp_bytes = s->resp ? bytes : 0;
+          if (!s->resp) ast = EVM_ENOMEM;
+        }
+        return s->resp;
+      },
+      U64P(rout), &total);
+  if (!st) st = ast;
+  if (st) return st;
+  std::vector<u64> ro((size_t)n + 1);
+  HIPR(hipMemcpyAsync(ro.data(), rout, sizeof(u64) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPR(hipStreamSynchronize(ctx->stream));
+  for (uint32_t k = 0; k <= n; ++k) resp_off[k] = ro[k] - ro[0];
+  *resp_bytes = total;
+  s->resp_used = total;
+  return EVM_OK;
+}
+
 int evm_sync_users(evm_sync_server* s, const uint8_t* ids, const uint64_t* id_off, uint32_t n, int insert,
                    uint32_t* slots) {
   if (!s || !id_off || !slots || (n && !ids)) return EVM_EINVAL;
@@ -1258,6 +1408,16 @@ int evm_sync_user_flag(evm_sync_server* s, uint32_t slot, int flag) {
   evm_ctx* ctx = s->ctx;
   KLAUNCH(k_set_u8, dim3(1), dim3(1), s->flag, slot, (uint8_t)flag);
   return hip_ok(hipStreamSynchronize(ctx->stream));
+}
+
+int evm_sync_user_flag_get(evm_sync_server* s, uint32_t slot, int* flag) {
+  if (!s || !flag || slot >= s->users) return EVM_EINVAL;
+  evm_ctx* ctx = s->ctx;
+  uint8_t f = 0;
+  HIPR(hipMemcpyAsync(&f, s->flag + slot, 1, hipMemcpyDeviceToHost, ctx->stream));
+  HIPR(hipStreamSynchronize(ctx->stream));
+  *flag = f ? 1 : 0;
+  return EVM_OK;
 }
 
 int evm_sync_user_count(const evm_sync_server* s, uint32_t* n_users, uint64_t* key_bytes) {

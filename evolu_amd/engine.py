@@ -125,6 +125,20 @@ class Engine:
             check(st, "evm_pack")
         return out, st
 
+    def classify_timestamps(self, rows: torch.Tensor):
+        """evolu_amd/lenient.py:classify on the device (evm_ts_classify): rows
+        (n, stride >= 46) uint8 -> (cls uint8 [n]: _lib.TS_OK / TS_RANGE_ERROR /
+        TS_UNSUPPORTED, canon uint8 [n, 46]: timestampToString(timestampFromString(row))
+        where cls is TS_OK, zero elsewhere)."""
+        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] < TS_LEN or not rows.is_contiguous():
+            raise ValueError("classify_timestamps: rows must be a contiguous (n, stride >= 46) uint8 tensor "
+                             "(a sliced view has another row stride than its shape says)")
+        n, stride = rows.shape
+        cls = torch.empty(n, dtype=torch.uint8, device=rows.device)
+        canon = torch.zeros((n, TS_LEN), dtype=torch.uint8, device=rows.device)
+        check(self.lib.evm_ts_classify(self.h, _ptr(rows), stride, n, _ptr(cls), _ptr(canon)), "evm_ts_classify")
+        return cls, canon
+
     # ----------------------------------------------------------------- trees
     def tree_new(self, n_owners: int = 1) -> "Trees":
         h = C.c_void_p()

@@ -31,6 +31,11 @@
  *                         request handler (parseBody, getMerkleTree,
  *                         addMessages, getMessages, toBinary), batched over
  *                         the requests of one round, bodies in and out
+ *   evm_ts_classify ..... timestamp.ts:43-55 timestampToString(
+ *                         timestampFromString(raw)) for strings outside the
+ *                         canonical form: its result, or the RangeError
+ *   evm_sync_export ..... apps/server/src/index.ts:64-75 one user's rows of
+ *                         the "message" and "merkleTree" tables
  */
 #ifndef EVM_H
 #define EVM_H
@@ -58,8 +63,10 @@ enum evm_status {
   EVM_EROUNDS = 11,   /* evm_sync_round: a userId in two requests of one call; nothing applied (split the call) */
   EVM_EHANDOVER = 12, /* evm_sync_round, per request: not modelled here (a nodeId that is not 16 hex chars, or a
                          user handed to the caller); nothing of it applied -- the caller's reference path runs it */
-  EVM_ESNAPSHOT = 13  /* evm_sync_load / evm_snapshot_info: the file is damaged, truncated or of an unknown
+  EVM_ESNAPSHOT = 13, /* evm_sync_load / evm_snapshot_info: the file is damaged, truncated or of an unknown
                          version, or the store rebuilt from it does not have the saved roots; nothing loaded */
+  EVM_EDATE = 14      /* evm_sync_round with EVM_SYNC_OPT_DATE_500, per request: a timestamp whose date V8's
+                         Date.parse rejects: toISOString throws -> 500; nothing stored; the user is not handed over */
 };
 
 /* ---- packed timestamp record (32 bytes, device) -------------------------
@@ -150,6 +157,30 @@ int evm_copy_d2h(evm_ctx* ctx, void* dst_host, const void* src_dev, size_t bytes
  * 48 is the coalesced native layout).  aux may be NULL.  Writes out[n].
  * Returns EVM_ENONCANON if any record lacks EVM_META_VALID (out still full). */
 int evm_pack(evm_ctx* ctx, const char* ts, size_t stride, size_t n, const uint32_t* aux, evm_rec* out);
+
+/* ---- what the reference makes of a timestamp outside the canonical form ---
+ * timestampFromString (timestamp.ts:50-55) Date.parse's whatever it is sent;
+ * the tree hashes timestampToString of the result (:43-48), whose toISOString
+ * throws a RangeError on an invalid date (the request then answers 500,
+ * index.ts:166-169).  Per row of 46 bytes (layout as evm_pack; rows at any
+ * byte alignment, nothing past a row's 46 bytes is read), cls[i] (device
+ * uint8 [n]) becomes
+ *   EVM_TS_OK           a string V8's ISO parser reads (fixed-width fields,
+ *                       'T'/'t' and 'Z'/'z', hour 24 only at :00:00.000, days
+ *                       29-31 rolling into the next month, a 4-hex counter and
+ *                       a 16-hex node in either case) with 0 <= millis < 2^31
+ *                       minutes: canon row i (device, 46 bytes per row, may be
+ *                       NULL) = timestampToString(timestampFromString(row)):
+ *                       the counter in upper case, the node as sent.  A
+ *                       canonical row is its own canon.
+ *   EVM_TS_RANGE_ERROR  that shape, but Date.parse is NaN (month 13, day 32,
+ *                       hour 25, 24:00:01, ...): canon row i is not written.
+ *   EVM_TS_UNSUPPORTED  any other string, or a date outside the native domain
+ *                       (before 1970, at or after 2^31 minutes): not modelled.  */
+#define EVM_TS_OK 0
+#define EVM_TS_RANGE_ERROR 1
+#define EVM_TS_UNSUPPORTED 2
+int evm_ts_classify(evm_ctx* ctx, const char* ts, size_t stride, size_t n, uint8_t* cls, uint8_t* canon);
 
 /* ---- Merkle trees: per-owner leaf maps, device resident -----------------
  * A tree set holds one MerkleTree per owner as the sorted list of its leaves:
@@ -355,6 +386,13 @@ int evm_server_select(evm_ctx* ctx, const evm_store* s, const evm_tree* client, 
 int evm_store_select_after(evm_ctx* ctx, const evm_store* s, const int64_t* bound, const char* node,
                            const uint8_t* active, uint64_t* sel_off, uint64_t* sel_id, uint64_t* sel_key,
                            uint64_t cap, uint64_t* n_sel);
+/* Every row of the owners with active[o] != 0 (device uint8 [n_owners]; NULL:
+ * all owners), in timestamp order, outputs as above: SELECT ... WHERE userId =
+ * ? ORDER BY timestamp.  Unlike a bound of 0 (which means timestamp >
+ * "1970-01-01T00:00:00.000Z-0000-0000000000000000" and so leaves out a row
+ * stored at exactly that string) no row is lost to a lower bound. */
+int evm_store_select_all(evm_ctx* ctx, const evm_store* s, const uint8_t* active, uint64_t* sel_off,
+                         uint64_t* sel_id, uint64_t cap, uint64_t* n_sel);
 
 /* ---------------------------------------------------------------- wire codec
  * protobuf.proto SyncRequest / SyncResponse (protobuf.ts:60-171), HOST
@@ -515,21 +553,61 @@ int evm_pb_encode_responses_dev(evm_ctx* ctx, uint32_t n, const evm_tree* tree, 
  * RangeError -> 500; rows committed), EVM_ENONCANON (a timestamp outside
  * the native domain: nothing of the request stored -- the caller's reference
  * path decides: RangeError of toISOString, or a lenient spelling V8
- * accepts), EVM_EHANDOVER (see the status).  resp_off: host n + 1;
+ * accepts), EVM_EHANDOVER (see the status), EVM_EDATE (only with
+ * EVM_SYNC_OPT_DATE_500, below).  resp_off: host n + 1;
  * *resp_bytes: the arena's size.  evm_sync_fetch copies the arena to host
  * memory; evm_sync_responses_dev returns it in device memory (valid until
- * the next round).
+ * the next round or evm_sync_export).
  *
  * The rest serves a caller that runs some requests on its own path (the
  * reference's, for EVM_ENONCANON / EVM_EHANDOVER) against the same store:
  * evm_sync_users looks up (insert != 0: and adds, in order) users given in
- * host memory -> slots; evm_sync_user_flag hands a user over (1: every later
- * request of it answers EVM_EHANDOVER) or takes it back (0); evm_sync_log_add
+ * host memory -> slots (UINT32_MAX: a user the directory does not hold, with
+ * insert == 0); evm_sync_user_flag hands a user over (1: every later
+ * request of it answers EVM_EHANDOVER) or takes it back (0), and
+ * evm_sync_user_flag_get reads the flag; evm_sync_log_add
  * appends rows ingested outside a round to the message log (host arrays:
  * ts rows of `stride` bytes, content_off n + 1 from 0, contents) and returns
  * their first message id (ids are consecutive, shared with the rounds);
  * evm_sync_log_read reads messages back by id (host: ts 46 B each,
- * content_off n + 1, contents; content NULL: sizes only). */
+ * content_off n + 1, contents; content NULL: sizes only).
+ *
+ * A call status is the verdict on the call, not on its transactions: a non-OK
+ * call status other than EVM_EROUNDS or EVM_ECAPACITY (an allocation or a HIP
+ * call that failed late in the round, say) can follow a committed addMessages
+ * -- rows of the call's requests may already be stored.
+ *
+ * evm_sync_set_option: two options, both 0 by default and neither part of a
+ * snapshot (set them again after evm_sync_load).  With both 0, or in a round
+ * that rejects no request, the round launches exactly the kernels it launches
+ * without them.
+ *   EVM_SYNC_OPT_DATE_500  1: the 46-byte rows the ingest flagged EVM_MSG_BAD
+ *     are classified (evm_ts_classify) and the classes reduced per request: a
+ *     rejected request with >= 1 EVM_TS_RANGE_ERROR row is answered EVM_EDATE
+ *     (the reference answers 500 with nothing stored, whatever else the
+ *     request holds) instead of EVM_ENONCANON.  Every other rejected request
+ *     stays EVM_ENONCANON -- one with a timestamp that is not 46 bytes too.
+ *   EVM_SYNC_OPT_HANDOVER  1: every request the round answers EVM_ENONCANON
+ *     has its user's hand-over flag set on the device inside that round (as
+ *     evm_sync_user_flag(slot, 1) would): the caller's reference path may
+ *     store that request's rows, so from the next round on the user's requests
+ *     answer EVM_EHANDOVER instead of being served from a store that lacks
+ *     them.  EVM_EDATE requests set no flag.
+ *
+ * evm_sync_export: what the reference's two tables hold for the users in
+ * slots[n] (host; a slot may repeat), as one SyncResponse body per slot built
+ * in the round's response arena: merkleTree = the stored tree's JSON ("{}"
+ * for a user without rows), messages = every stored row of that owner in
+ * timestamp order with the log's 46 bytes and its content -- no node filter
+ * and no lower bound (the row at millis 0, counter 0, node 0000000000000000
+ * included).  It serves handed-over users as any other: it is how the caller
+ * seeds its reference database before running such a user's requests there.
+ * resp_off (host, n + 1) / *resp_bytes as in a round; the arena is read with
+ * evm_sync_fetch or evm_sync_responses_dev, and THE LAST ROUND'S RESPONSES
+ * BECOME INVALID (the arena is reused).  A slot at or beyond the user count:
+ * EVM_EINVAL with nothing built. */
+#define EVM_SYNC_OPT_DATE_500 1
+#define EVM_SYNC_OPT_HANDOVER 2
 #define EVM_SYNC_HOST 0
 #define EVM_SYNC_DEVICE 1
 typedef struct evm_sync_server evm_sync_server;
@@ -539,9 +617,12 @@ int evm_sync_round(evm_sync_server* s, const uint8_t* arena, const uint64_t* off
                    int32_t* result, uint64_t* resp_off, uint64_t* resp_bytes);
 int evm_sync_fetch(evm_sync_server* s, uint8_t* out);
 const uint8_t* evm_sync_responses_dev(const evm_sync_server* s);
+int evm_sync_set_option(evm_sync_server* s, int option, int64_t value);
+int evm_sync_export(evm_sync_server* s, const uint32_t* slots, uint32_t n, uint64_t* resp_off, uint64_t* resp_bytes);
 int evm_sync_users(evm_sync_server* s, const uint8_t* ids, const uint64_t* id_off, uint32_t n, int insert,
                    uint32_t* slots);
 int evm_sync_user_flag(evm_sync_server* s, uint32_t slot, int flag);
+int evm_sync_user_flag_get(evm_sync_server* s, uint32_t slot, int* flag); /* *flag: 1 handed over, 0 not */
 int evm_sync_user_count(const evm_sync_server* s, uint32_t* n_users, uint64_t* key_bytes);
 int evm_sync_user_keys(evm_sync_server* s, uint8_t* keys, uint64_t* key_off);
 int evm_sync_log_add(evm_sync_server* s, const char* ts, size_t stride, uint64_t n, const uint64_t* content_off,

@@ -1272,6 +1272,9 @@ napi_value SyncDestroy(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+napi_value sync_result(napi_env env, int st, uint32_t n, const int32_t* res, const uint64_t* roff, uint64_t total,
+                       void** resp_bytes);
+
 // syncRound(ctx, server, bodies Uint8Array, offsets Float64Array(n + 1))
 //   -> { status, results: Int32Array(n), offsets: Float64Array(n + 1), responses: Uint8Array }
 // status EVM_EROUNDS (a userId twice: nothing applied) leaves the rest empty.
@@ -1296,25 +1299,208 @@ napi_value SyncRound(napi_env env, napi_callback_info info) {
   const int st = evm_sync_round(srv, (const uint8_t*)body, off.data(), n, EVM_SYNC_HOST, res.data(), roff.data(),
                                 &total);
   if (st != EVM_OK && st != EVM_EROUNDS) return throw_status(env, st, "evm_sync_round");
+  void* p = nullptr;
+  napi_value out = sync_result(env, st, n, res.data(), roff.data(), total, &p);
+  if (p && total) {
+    const int fs = evm_sync_fetch(srv, (uint8_t*)p);
+    if (fs) return throw_status(env, fs, "evm_sync_fetch");
+  }
+  return out;
+}
+
+// syncRoundAsync(same arguments) -> Promise of syncRound's result.  The round
+// (staging in, the device round, the responses staged out) runs on libuv's
+// pool with the context locked and bound to that thread; the bodies are held
+// by a reference until it completes (the offsets are copied).  A call error rejects
+// the Promise with the Error syncRound would throw.  Two rounds queued at once
+// have no order on the pool: the caller chains them (SyncServer#syncAsync).
+struct SyncJob {
+  Ctx* cx = nullptr;
+  evm_sync_server* srv = nullptr;
+  const uint8_t* body = nullptr;
+  uint32_t n = 0;
+  std::vector<uint64_t> off, roff;
+  std::vector<int32_t> res;
+  std::vector<uint8_t> resp;
+  uint64_t total = 0;
+  int status = EVM_OK;
+  const char* where = "evm_sync_round";
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  napi_ref body_ref = nullptr;  // the bodies' typed array, held until completion
+};
+
+napi_value sync_result(napi_env env, int st, uint32_t n, const int32_t* res, const uint64_t* roff, uint64_t total,
+                       void** resp_bytes) {
   napi_value out, v;
   napi_create_object(env, &out);
   napi_create_int32(env, st, &v);
   napi_set_named_property(env, out, "status", v);
+  *resp_bytes = nullptr;
   if (st == EVM_EROUNDS) return out;
   void* p;
   napi_value vr = typed(env, napi_int32_array, n, 4, &p);
-  if (n) memcpy(p, res.data(), 4 * (size_t)n);
+  if (n) memcpy(p, res, 4 * (size_t)n);
   napi_set_named_property(env, out, "results", vr);
-  napi_value vo = typed(env, napi_float64_array, n1, 8, &p);
-  for (size_t k = 0; k < n1; ++k) static_cast<double*>(p)[k] = (double)roff[k];
+  napi_value vo = typed(env, napi_float64_array, (size_t)n + 1, 8, &p);
+  for (size_t k = 0; k <= n; ++k) static_cast<double*>(p)[k] = (double)roff[k];
   napi_set_named_property(env, out, "offsets", vo);
-  napi_value vb = typed(env, napi_uint8_array, (size_t)total, 1, &p);
-  if (total) {
-    const int fs = evm_sync_fetch(srv, (uint8_t*)p);
-    if (fs) return throw_status(env, fs, "evm_sync_fetch");
-  }
+  napi_value vb = typed(env, napi_uint8_array, (size_t)total, 1, resp_bytes);
   napi_set_named_property(env, out, "responses", vb);
   return out;
+}
+
+void sync_execute(napi_env, void* data) {
+  SyncJob* j = static_cast<SyncJob*>(data);
+  std::lock_guard<std::mutex> lock(j->cx->m);
+  j->status = evm_bind_thread(j->cx->c);
+  if (j->status) {
+    j->where = "evm_bind_thread";
+    return;
+  }
+  j->status = evm_sync_round(j->srv, j->body, j->off.data(), j->n, EVM_SYNC_HOST, j->res.data(), j->roff.data(),
+                             &j->total);
+  if (j->status != EVM_OK || !j->total) return;
+  j->resp.resize((size_t)j->total);
+  j->status = evm_sync_fetch(j->srv, j->resp.data());
+  if (j->status) j->where = "evm_sync_fetch";
+}
+
+void sync_complete(napi_env env, napi_status, void* data) {
+  SyncJob* j = static_cast<SyncJob*>(data);
+  if (j->status != EVM_OK && j->status != EVM_EROUNDS) {
+    const std::string m = std::string(j->where) + ": " + evm_strerror(j->status);
+    napi_value code, msg, err;
+    napi_create_string_utf8(env, std::to_string(j->status).c_str(), NAPI_AUTO_LENGTH, &code);
+    napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+    napi_create_error(env, code, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else {
+    void* p = nullptr;
+    napi_value out = sync_result(env, j->status, j->n, j->res.data(), j->roff.data(), j->total, &p);
+    if (p && j->total) memcpy(p, j->resp.data(), (size_t)j->total);
+    napi_resolve_deferred(env, j->deferred, out);
+  }
+  if (j->body_ref) napi_delete_reference(env, j->body_ref);
+  napi_delete_async_work(env, j->work);
+  delete j;
+}
+
+napi_value SyncRoundAsync(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return nullptr;
+  void *body, *offd;
+  size_t bl, ol;
+  if (!bytes_of(env, a[2], &body, &bl) || !bytes_of(env, a[3], &offd, &ol)) return nullptr;
+  const size_t n1 = ol / 8;
+  if (n1 < 1) return throw_status(env, EVM_EINVAL, "syncRoundAsync: offsets");
+  SyncJob* j = new SyncJob();
+  j->cx = ctx_of(env, a[0]);
+  j->srv = (evm_sync_server*)ext(env, a[1]);
+  j->body = (const uint8_t*)body;
+  j->n = (uint32_t)(n1 - 1);
+  j->off.resize(n1);
+  j->roff.assign(n1, 0);
+  j->res.assign(j->n, 0);
+  for (size_t k = 0; k < n1; ++k) j->off[k] = (uint64_t)static_cast<const double*>(offd)[k];
+  if (j->off[j->n] > bl) {
+    delete j;
+    return throw_status(env, EVM_EINVAL, "syncRoundAsync: offsets past the bodies");
+  }
+  // (only the bodies are read on the pool: the offsets were copied above)
+  napi_value promise, name;
+  if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
+    delete j;
+    napi_throw_error(env, nullptr, "syncRoundAsync: napi_create_promise failed");
+    return nullptr;
+  }
+  // from here on every failure settles the Promise: a caller that counts pending calls is never left waiting
+  const char* failed = nullptr;
+  if (napi_create_reference(env, a[2], 1, &j->body_ref) != napi_ok) failed = "napi_create_reference";
+  else if (napi_create_string_utf8(env, "evolu_evm.syncRound", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+           napi_create_async_work(env, nullptr, name, sync_execute, sync_complete, j, &j->work) != napi_ok)
+    failed = "napi_create_async_work";
+  else if (napi_queue_async_work(env, j->work) != napi_ok) failed = "napi_queue_async_work";
+  if (failed) {
+    const std::string m = std::string("syncRoundAsync: ") + failed + " failed; the round was not run";
+    napi_value msg, err;
+    napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+    napi_create_error(env, nullptr, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+    if (j->work) napi_delete_async_work(env, j->work);
+    if (j->body_ref) napi_delete_reference(env, j->body_ref);
+    delete j;
+  }
+  return promise;
+}
+
+// syncSetOption(ctx, server, option, value): evm_sync_set_option
+napi_value SyncSetOption(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return nullptr;
+  Ctx* cx = ctx_of(env, a[0]);
+  std::lock_guard<std::mutex> lock(cx->m);
+  const int st = evm_sync_set_option((evm_sync_server*)ext(env, a[1]), (int)u32(env, a[2]), (int64_t)u32(env, a[3]));
+  if (st) return throw_status(env, st, "evm_sync_set_option");
+  return nullptr;
+}
+
+std::string string_of(napi_env env, napi_value v);
+
+// a known user's slot (no insert); false: the directory does not hold userId
+bool slot_of(evm_sync_server* srv, const std::string& u, uint32_t* slot, int* st) {
+  const uint64_t uo[2] = {0, (uint64_t)u.size()};
+  *slot = 0xffffffffu;
+  *st = evm_sync_users(srv, (const uint8_t*)u.data(), uo, 1, 0, slot);
+  uint32_t users = 0;
+  if (!*st) *st = evm_sync_user_count(srv, &users, nullptr);
+  return !*st && *slot < users;
+}
+
+// syncExport(ctx, server, userId string) -> Uint8Array (the user's SyncResponse: every stored row and
+// the stored tree, evm_sync_export) | null for a userId the directory does not hold
+napi_value SyncExport(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return nullptr;
+  Ctx* cx = ctx_of(env, a[0]);
+  std::lock_guard<std::mutex> lock(cx->m);
+  evm_sync_server* srv = (evm_sync_server*)ext(env, a[1]);
+  uint32_t slot;
+  int st;
+  napi_value v;
+  if (!slot_of(srv, string_of(env, a[2]), &slot, &st)) {
+    if (st) return throw_status(env, st, "syncExport: evm_sync_users");
+    napi_get_null(env, &v);
+    return v;
+  }
+  uint64_t roff[2] = {0, 0}, total = 0;
+  st = evm_sync_export(srv, &slot, 1, roff, &total);
+  if (st) return throw_status(env, st, "evm_sync_export");
+  void* p;
+  v = typed(env, napi_uint8_array, (size_t)total, 1, &p);
+  if (total && (st = evm_sync_fetch(srv, (uint8_t*)p))) return throw_status(env, st, "evm_sync_fetch");
+  return v;
+}
+
+// syncUserFlagGet(ctx, server, userId string) -> true / false (handed over or not) | null (unknown user)
+napi_value SyncUserFlagGet(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return nullptr;
+  Ctx* cx = ctx_of(env, a[0]);
+  std::lock_guard<std::mutex> lock(cx->m);
+  evm_sync_server* srv = (evm_sync_server*)ext(env, a[1]);
+  uint32_t slot;
+  int st, flag = 0;
+  napi_value v;
+  if (!slot_of(srv, string_of(env, a[2]), &slot, &st)) {
+    if (st) return throw_status(env, st, "syncUserFlagGet: evm_sync_users");
+    napi_get_null(env, &v);
+    return v;
+  }
+  st = evm_sync_user_flag_get(srv, slot, &flag);
+  if (st) return throw_status(env, st, "evm_sync_user_flag_get");
+  napi_get_boolean(env, flag != 0, &v);
+  return v;
 }
 
 // syncUserFlag(ctx, server, userId string, flag): hand a user to the caller's path (1) or back (0)
@@ -1429,7 +1615,9 @@ napi_value Init(napi_env env, napi_value exports) {
              {"distHotOwners", DistHotOwners}, {"distSplit", DistSplit},   {"distSelectSplit", DistSelectSplit},
              {"distSplitApply", DistSplitApply}, {"syncCreate", SyncCreate}, {"syncDestroy", SyncDestroy},
              {"syncRound", SyncRound},       {"syncUserFlag", SyncUserFlag}, {"syncCompact", SyncCompact},
-             {"syncSave", SyncSave},         {"syncLoad", SyncLoad},         {"syncLogInfo", SyncLogInfo}};
+             {"syncSave", SyncSave},         {"syncLoad", SyncLoad},         {"syncLogInfo", SyncLogInfo},
+             {"syncRoundAsync", SyncRoundAsync}, {"syncSetOption", SyncSetOption}, {"syncExport", SyncExport},
+             {"syncUserFlagGet", SyncUserFlagGet}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -45,8 +45,11 @@ function encodeTimestamps(strings) {
 class Engine {
   constructor(device = 0) {
     this.ctx = addon.create(device);
+    this._pending = 0;  // SyncServer#syncAsync calls of this engine's servers not yet settled
   }
   close() {
+    // (a round on libuv's pool holds the context: destroying it under the round is a use after free)
+    if (this._pending) throw new Error("Engine#close: a syncAsync call is pending; await it first");
     if (this.ctx) addon.destroy(this.ctx);
     this.ctx = null;
   }
@@ -294,19 +297,51 @@ class Server {
 // directory, addMessages, getMessages and SyncResponse.toBinary on the device.
 // sync(bodies: Uint8Array[]) -> per body the response bytes (Uint8Array), 500
 // (the handler's res.status(500): a body that does not parse, a client tree
-// merkleTreeFromString rejects, a RangeError of the diff), or null: not
-// applied here -- a timestamp outside the engine's domain, a nodeId that is not
-// 16 hex chars, a non-ASCII userId, or a user handed over (handOver): the
-// reference's handler runs it.  A user with two requests in one call gets them
-// in rounds, in order (the k-th request of every user in round k).
+// merkleTreeFromString rejects, a RangeError of the diff, a timestamp whose
+// date Date.parse rejects -- toISOString throws, nothing stored), or null: not
+// applied here, and THIS USER IS THE CALLER'S FROM THIS REQUEST ON -- a
+// timestamp in a lenient spelling or outside the engine's domain, a nodeId
+// that is not 16 hex chars, a non-ASCII userId, or a user handed over before.
+// The reference's handler runs it and every later request of that user (the
+// device sets the user's hand-over flag inside the round, so a later request
+// is never answered from a store that lacks what the reference path stored);
+// exportUser(userId) gives the rows and the tree the device holds for the
+// user, to seed the reference database first.  A user with two requests in one
+// call gets them in rounds, in order (the k-th request of every user in round k).
+//
+// syncAsync(bodies) is the same as a Promise: every round runs on libuv's pool
+// (addon.syncRoundAsync), the event loop stays free.  Calls issued without
+// awaiting are applied in issue order (they are chained on this server, not
+// left to the pool's threads).  The rule while such a call is pending, for
+// every method of this class and for Engine#close:
+//   * what destroys, rewrites or reorders state THROWS (await the Promise
+//     first): close(), Engine#close(), save(), compact(), and the blocking
+//     sync(), whose rounds would otherwise run between the pending call's;
+//   * what reads or flags one user WORKS, from any continuation, with other
+//     calls pending: exportUser(), isHandedOver(), handOver(), logInfo().
+//     They take the context's mutex in the addon, so they block the JS thread
+//     for at most the one round in flight.  That is safe: a round copies its
+//     responses out before it releases the mutex (an export reusing the
+//     response arena cannot clobber them), and a user answered null is
+//     flagged, so no pending round changes the rows exportUser returns.
 const EVM_EROUNDS = 11;
 const SYNC_ANSWERED = 0;
-const SYNC_500 = new Set([1 /* EVM_EINVAL */, 4 /* EVM_ERANGE */, 5 /* EVM_ETREE */]);
+const SYNC_500 = new Set([1 /* EVM_EINVAL */, 4 /* EVM_ERANGE */, 5 /* EVM_ETREE */, 14 /* EVM_EDATE */]);
+const SYNC_OPT_DATE_500 = 1;
+const SYNC_OPT_HANDOVER = 2;
 class SyncServer {
   constructor(engine, nUsers, loaded = null) {
     this.engine = engine;
     this.store = loaded ? loaded.store : addon.storeNew(engine.ctx, nUsers);
     this.h = loaded ? loaded.h : addon.syncCreate(engine.ctx, this.store);
+    // (the options are not part of a snapshot: a loaded server gets them here too)
+    addon.syncSetOption(engine.ctx, this.h, SYNC_OPT_DATE_500, 1);
+    addon.syncSetOption(engine.ctx, this.h, SYNC_OPT_HANDOVER, 1);
+    this._chain = Promise.resolve();  // the last syncAsync call (never rejects)
+    this._pending = 0;                // syncAsync calls not yet settled
+  }
+  _idle(what) {
+    if (this._pending) throw new Error(`SyncServer#${what}: a syncAsync call is pending; await it first`);
   }
   // A server read back from save()'s file into a new store of nUsers owner
   // slots (at least the saved users; more lets new users in): the state
@@ -325,10 +360,12 @@ class SyncServer {
   }
   // the message log reduced to the stored rows, in one segment
   compact() {
+    this._idle("compact");
     addon.syncCompact(this.engine.ctx, this.h);
   }
   // compacts, then writes the server to path (path + ".tmp", fsync, rename)
   save(path) {
+    this._idle("save");
     addon.syncSave(this.engine.ctx, this.h, path);
   }
   // { segments, rows, contentBytes } of the message log
@@ -336,41 +373,90 @@ class SyncServer {
     return addon.syncLogInfo(this.engine.ctx, this.h);
   }
   close() {
+    this._idle("close");
     addon.syncDestroy(this.engine.ctx, this.h);
     addon.storeFree(this.engine.ctx, this.store);
   }
   handOver(userId, flag = true) {
     addon.syncUserFlag(this.engine.ctx, this.h, userId, flag ? 1 : 0);
   }
+  // true: the user's requests are the caller's (handOver, or a request answered null);
+  // false: served here; null: a userId this server has never seen
+  isHandedOver(userId) {
+    return addon.syncUserFlagGet(this.engine.ctx, this.h, userId);
+  }
+  // What the reference's two tables would hold for userId, as SyncResponse bytes
+  // (evm_sync_export): merkleTree = the stored tree, messages = every stored row in
+  // timestamp order with its content -- for a handed-over user too (that is its
+  // purpose: seed the reference database, then run the user's requests there).
+  // null: a userId this server has never seen.
+  exportUser(userId) {
+    return addon.syncExport(this.engine.ctx, this.h, userId);
+  }
+  // the k-th request of every user in round k (a body that does not parse: round 0, answered 500 there)
+  _rounds(bodies) {
+    const seen = new Map();
+    const rounds = [];
+    bodies.forEach((b, i) => {
+      let u = null;
+      try {
+        u = SyncRequest.fromBinary(b).userId;
+      } catch (e) {
+        u = null;  // (answered 500 by the round)
+      }
+      const k = u === null ? 0 : (seen.get(u) || 0);
+      if (u !== null) seen.set(u, k + 1);
+      while (rounds.length <= k) rounds.push([]);
+      rounds[k].push(i);
+    });
+    return rounds;
+  }
   sync(bodies) {
+    this._idle("sync");
     const out = new Array(bodies.length).fill(null);
     if (!this._round(bodies, bodies.map((_, i) => i), out)) {
-      const seen = new Map();
-      const rounds = [];
-      bodies.forEach((b, i) => {
-        let u = null;
-        try {
-          u = SyncRequest.fromBinary(b).userId;
-        } catch (e) {
-          u = null;  // (answered 500 by the round)
-        }
-        const k = u === null ? 0 : (seen.get(u) || 0);
-        if (u !== null) seen.set(u, k + 1);
-        while (rounds.length <= k) rounds.push([]);
-        rounds[k].push(i);
-      });
-      for (const idx of rounds) {
+      for (const idx of this._rounds(bodies)) {
         if (!this._round(idx.map((i) => bodies[i]), idx, out)) throw new Error("syncRound: a userId twice in a round");
       }
     }
     return out;
   }
-  _round(bodies, idx, out) {
+  // -> Promise of sync(bodies)'s result; rejects if a round fails as a call
+  syncAsync(bodies) {
+    const run = () => this._syncAsync(bodies);
+    const p = this._chain.then(run);
+    const settled = () => { this._pending--; this.engine._pending--; };
+    this._pending++;
+    this.engine._pending++;
+    this._chain = p.then(settled, settled);
+    return p;
+  }
+  async _syncAsync(bodies) {
+    const out = new Array(bodies.length).fill(null);
+    if (!(await this._roundAsync(bodies, bodies.map((_, i) => i), out))) {
+      for (const idx of this._rounds(bodies)) {
+        if (!(await this._roundAsync(idx.map((i) => bodies[i]), idx, out)))
+          throw new Error("syncRound: a userId twice in a round");
+      }
+    }
+    return out;
+  }
+  _arena(bodies) {
     const off = new Float64Array(bodies.length + 1);
     bodies.forEach((b, i) => { off[i + 1] = off[i] + b.length; });
     const arena = new Uint8Array(off[bodies.length]);
     bodies.forEach((b, i) => arena.set(b, off[i]));
-    const r = addon.syncRound(this.engine.ctx, this.h, arena, off);
+    return [arena, off];
+  }
+  _round(bodies, idx, out) {
+    const [arena, off] = this._arena(bodies);
+    return this._answers(addon.syncRound(this.engine.ctx, this.h, arena, off), bodies, idx, out);
+  }
+  async _roundAsync(bodies, idx, out) {
+    const [arena, off] = this._arena(bodies);
+    return this._answers(await addon.syncRoundAsync(this.engine.ctx, this.h, arena, off), bodies, idx, out);
+  }
+  _answers(r, bodies, idx, out) {
     if (r.status === EVM_EROUNDS) return false;
     for (let k = 0; k < bodies.length; k++) {
       const code = r.results[k];
